@@ -3,22 +3,42 @@
 
 One step = one lvlip_csum_batch_dev launch over one synthetic batch already
 resident in HBM (BASELINE.json configs[1] by default: 1 M x 1500 B TCP
-segments).  Prints ONE JSON line (rank 0):
+segments).  A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets the
+batch up, settles and warms up, times the K steps, writes the outputs when
+--dump-outputs is given, and prints ONE JSON line (rank 0):
 
   value       whole-job GB/s = sum over ranks of algorithmic bytes x K / max-over-ranks time
+  ms_per_step  the slowest rank's wall time over the K timed steps / K, in ms
   roofline    the checksum kernel's achieved algorithmic GB/s (HIP events on the launch
-              stream) against the 8 TB/s HBM3E peak; frac_aggregate = value / (N x 8 TB/s);
-              traffic = PMC-measured HBM bytes per launch from profiles/ when a matching
-              measurement is committed (traffic_source names the file: the builder's
-              box, not this run's), else null; achieved_contract / frac_contract
+              stream around the same K steps) against the 8 TB/s HBM3E peak;
+              frac_aggregate = value / (N x 8 TB/s); achieved_contract / frac_contract
               count SURVEY.md §8(d)'s algorithmic bytes exactly (the bytes summed +
               2 B per result; achieved counts the summed bytes only, 0.13 % less)
+
+Everything else the benchmark measures or checks runs with --full only (null
+in a plain run's line):
+
+  roofline.traffic  PMC-measured HBM bytes per launch from profiles/ when a matching
+              measurement is committed (traffic_source names the file: the builder's
+              box, not this run's), else null
   verified_bit_exact  every one of the N outputs of the timed batch, copied back from
               HBM after the timed loop, equals level-ip's own checksum() (oracle/_ref,
               compiled from src/utils.c) run over the same bytes; on every rank
+              (--no-verify leaves it out)
   cpu_baseline  that reference checksum() on the host cores (rank 0, N=1): all
               cores of the process's affinity mask over the whole timed batch, plus
-              one-core and 16-thread figures
+              one-core and 16-thread figures (--no-cpu-baseline leaves it out)
+  diag.read_probe_GBps  the lab's streaming-read probes over the same buffer
+
+--sweep, --frames, --crossover and --e2e add their own diagnostics to either
+kind of run.
+
+--dump-outputs DIR writes what the last timed step left in the output buffer,
+the N checksums a caller of lvlip_csum_batch_dev receives, as DIR/checksums.npy
+(float32, exact for 16-bit values; checksums_rank<r>.npy with N > 1 ranks).  An
+output above the 64 MB budget (shared by the ranks) is cut to a fixed seeded
+sample, whose indices go to DIR/checksums_index.npy (float64).  The batch is a
+pure function of the arguments, so two builds can be compared output for output.
 
 Before the W warm-up steps every rank runs untimed steps for --settle-ms of wall
 time (default 250 ms), so the timed region starts at the GPU's sustained clocks
@@ -63,6 +83,8 @@ WORKLOAD_TEXT = {
 }
 STRONG = {"tcp1500x64m": 64 << 20}  # workload -> total packets over all ranks
 VERIFY_SPAN = 2 << 30  # host bytes per verification chunk (copied back from HBM)
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much, over all ranks and files
+DUMP_SEED = 0x1E7E1C5  # of the sample taken from a larger output
 
 
 def parse(argv=None):
@@ -83,8 +105,15 @@ def parse(argv=None):
                    choices=["auto", "wave", "flat", "window", "wflat", "lane"])
     p.add_argument("--unroll", type=int, default=0)
     p.add_argument("--waves-per-cu", type=int, default=0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-verify", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="beside the timed steps: check every output of the timed batch against "
+                        "the reference, time the CPU baseline, run the read probes and look up "
+                        "the PMC traffic (a plain run does none of these)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's checksums to "
+                        "DIR/checksums.npy (float32; at most 64 MB, a seeded sample beyond that)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    p.add_argument("--no-verify", action="store_true", help="with --full: no check against the reference")
     p.add_argument("--dry-run", action="store_true",
                    help="rehearse the launch / rendezvous / report path on the CPU (gloo, no "
                         "GPU work, small batch): the line carries dry_run=true and no throughput")
@@ -285,6 +314,30 @@ def cpu_baseline(b, first, cpus: dict, budget_s: float = 1.0):
         "one_core_O2_restatement_GBps": round(o2, 3),
         "dropin_one_core_GBps": round(dropin, 3),
     }
+
+
+# ------------------------------------------------------------- output dump --
+
+def dump_outputs(dirpath: str, out, n: int, rank: int, world: int) -> dict:
+    """--dump-outputs: the n checksums the last timed step wrote (what a caller
+    of lvlip_csum_batch_dev receives in `out`), copied back from HBM, as
+    float32 in dirpath/checksums.npy (checksums_rank<r>.npy with several
+    ranks).  Beyond this rank's share of DUMP_BYTES a fixed seeded sample is
+    written instead, its (sorted) indices as float64 beside it."""
+    got = out[:n].cpu().numpy().view(np.uint16)
+    os.makedirs(dirpath, exist_ok=True)
+    name = "checksums" if world == 1 else f"checksums_rank{rank}"
+    budget = DUMP_BYTES // world
+    files = {}
+    if got.size * 4 > budget:
+        k = budget // 12  # 4 B per value + 8 B per index
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(got.size, size=k, replace=False))
+        got = got[idx]
+        files[name + "_index.npy"] = idx.astype(np.float64)
+    files[name + ".npy"] = got.astype(np.float32)
+    for fn, arr in files.items():
+        np.save(os.path.join(dirpath, fn), arr)
+    return {"dir": dirpath, "files": sorted(files), "values": int(got.size), "of": n}
 
 
 # ------------------------------------------------------------------ launcher --
@@ -517,11 +570,15 @@ def run(args, world: int):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max = float(t[0])
 
-    # every rank checks its whole timed batch (all N outputs) against the
-    # reference over the same bytes, copied back from HBM
+    dumped = None
+    if args.dump_outputs and not args.dry_run:
+        dumped = dump_outputs(args.dump_outputs, out, b.n, rank, world)
+
+    # --full: every rank checks its whole timed batch (all N outputs) against
+    # the reference over the same bytes, copied back from HBM
     cpus = host_cpus()
     verify, first_chunk = None, None
-    if not args.no_verify and not args.dry_run:
+    if args.full and not args.no_verify and not args.dry_run:
         thr = max(1, usable_cpus(cpus) // max(1, local_world))
         verify, first_chunk = verify_timed_batch(
             b, base, out, thr, keep_first=(rank == 0 and world == 1 and not args.no_cpu_baseline))
@@ -563,10 +620,12 @@ def run(args, world: int):
         diag["verify"] = verify
     if scatter_diag is not None:
         diag["scatter"] = scatter_diag
+    if dumped is not None:
+        diag["dump_outputs"] = dumped
     if rank == 0 and not args.dry_run:
         if args.sweep:
             diag["sweep"] = sweep(lvlip, torch, base, descs, out, b, stream)
-        if base.numel() < (1 << 34):
+        if args.full and base.numel() < (1 << 34):
             diag["read_probe_GBps"] = read_probe(lvlip, torch, base, stream)
         if args.frames:
             diag["frames_dev"] = frames_dev(lvlip, torch, dev)
@@ -582,7 +641,9 @@ def run(args, world: int):
         cpu = cpu_baseline(b, first_chunk, cpus)
 
     if rank == 0:
-        tr = traffic_from_profiles(args.workload, kernel_label, KERNEL_FN.get(chosen, ""))
+        tr = None
+        if args.full:
+            tr = traffic_from_profiles(args.workload, kernel_label, KERNEL_FN.get(chosen, ""))
         rec = {
             "metric": METRIC, "value": None if args.dry_run else round(value, 2), "unit": "GB/s",
             "n_gpus": world,

@@ -16,11 +16,11 @@ D=gpurun_out/evidence_${TAG}_${WL}
 mkdir -p $D
 step() { local rc; "$@"; rc=$?; if [ $rc -ne 0 ]; then echo "step failed rc=$rc: $*"; exit $rc; fi; }
 # 1. the bench line itself (default steps/warm-up, cpu_baseline included)
-step timeout -k 10 180 python3 bench.py --workload $WL $EXTRA > $D/bench.json 2> $D/bench.err
+step timeout -k 10 180 python3 bench.py --full --workload $WL $EXTRA > $D/bench.json 2> $D/bench.err
 # 2. the same command under the kernel trace
 step timeout -k 10 240 /opt/rocm/bin/rocprofv3 --kernel-trace --stats -T --output-format csv \
-    -d $D/trace -o trace -- python3 bench.py --workload $WL $EXTRA > $D/trace.json 2> $D/trace.err
+    -d $D/trace -o trace -- python3 bench.py --full --workload $WL $EXTRA > $D/trace.json 2> $D/trace.err
 # 3. PMC passes (one counter group per run), short runs
-OUT=$D/prof KRE=$KRE BENCH="bench.py --workload $WL --steps 20 --warmup 3 --settle-ms 0 --no-cpu-baseline $EXTRA" \
+OUT=$D/prof KRE=$KRE BENCH="bench.py --full --workload $WL --steps 20 --warmup 3 --settle-ms 0 --no-cpu-baseline $EXTRA" \
     step bash scripts/profile.sh
 echo "evidence in $D"

@@ -10,6 +10,8 @@ timeout -k 10 ${PYTEST_TIMEOUT:-900} python -m pytest tests -m gpu -x -q ${PYTES
 rc=$?
 tail -5 gpurun_out/pytest_gpu.log
 if [ $rc -ne 0 ]; then echo "pytest rc=$rc: stopping before the bench (a failed GPU test may be a fault)"; exit $rc; fi
+# --full: the line with every output verified, the CPU baseline and the read probes
+BENCH_ARGS=${BENCH_ARGS:---full --sweep --e2e}
 timeout -k 10 ${BENCH_TIMEOUT:-400} python bench.py ${BENCH_ARGS:---sweep --e2e} > gpurun_out/bench.json 2> gpurun_out/bench.err
 brc=$?
 cat gpurun_out/bench.json; tail -30 gpurun_out/bench.err

@@ -45,16 +45,16 @@ for step in "$@"; do
   case "$step" in
     tests) run tests 900 python -u -m pytest tests -m gpu -x -v --timeout 240 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 300 python bench.py ;;
-    bench:*) wl=${step#bench:}; run "bench_$wl" 300 python bench.py --workload "$wl" ;;
-    e2e) run e2e_tcp1500 300 python bench.py --e2e ;;
-    e2e:*) wl=${step#e2e:}; run "e2e_$wl" 300 python bench.py --workload "$wl" --e2e ;;
-    frames) run frames 600 python bench.py --workload mixed --frames ;;
-    rehearse:*) n=${step#rehearse:}; run "rehearse_n$n" 300 env LVLIP_DIST_BACKEND=gloo python bench.py --gpus "$n" --steps 50 --warmup 10 ;;
-    rehearse_strong:*) n=${step#rehearse_strong:}; run "rehearse_strong_n$n" 400 env LVLIP_DIST_BACKEND=gloo python bench.py --gpus "$n" --workload tcp1500x64m --steps 20 --warmup 5 ;;
-    rehearse_root:*) n=${step#rehearse_root:}; run "rehearse_root_n$n" 300 env LVLIP_DIST_BACKEND=gloo python bench.py --gpus "$n" --origin root --steps 50 --warmup 10 ;;
-    crossover) run crossover 600 python bench.py --crossover --steps 5 --warmup 2 --no-cpu-baseline ;;
-    crossover_t1) run crossover_t1 600 env LVLIP_GATHER_THREADS=1 python bench.py --crossover --steps 5 --warmup 2 \
+    bench) run bench 300 python bench.py --full ;;
+    bench:*) wl=${step#bench:}; run "bench_$wl" 300 python bench.py --full --workload "$wl" ;;
+    e2e) run e2e_tcp1500 300 python bench.py --full --e2e ;;
+    e2e:*) wl=${step#e2e:}; run "e2e_$wl" 300 python bench.py --full --workload "$wl" --e2e ;;
+    frames) run frames 600 python bench.py --full --workload mixed --frames ;;
+    rehearse:*) n=${step#rehearse:}; run "rehearse_n$n" 300 env LVLIP_DIST_BACKEND=gloo python bench.py --full --gpus "$n" --steps 50 --warmup 10 ;;
+    rehearse_strong:*) n=${step#rehearse_strong:}; run "rehearse_strong_n$n" 400 env LVLIP_DIST_BACKEND=gloo python bench.py --full --gpus "$n" --workload tcp1500x64m --steps 20 --warmup 5 ;;
+    rehearse_root:*) n=${step#rehearse_root:}; run "rehearse_root_n$n" 300 env LVLIP_DIST_BACKEND=gloo python bench.py --full --gpus "$n" --origin root --steps 50 --warmup 10 ;;
+    crossover) run crossover 600 python bench.py --full --crossover --steps 5 --warmup 2 --no-cpu-baseline ;;
+    crossover_t1) run crossover_t1 600 env LVLIP_GATHER_THREADS=1 python bench.py --full --crossover --steps 5 --warmup 2 \
                     --no-cpu-baseline ;;
     compose) run compose 900 sh -c "python scripts/compose_timing.py > gpurun_out/${TAG}_compose.json" ;;
     dispatch) run dispatch 900 python -u -m pytest tests/test_dispatch_gpu.py tests/test_ref_tx_batch.py \
@@ -69,7 +69,7 @@ for step in "$@"; do
         run "evidence_$wl" 900 env TAG="$TAG" WL="$wl" KRE="$kre" bash scripts/evidence.sh
       else  # the PMC passes alone, into the same evidence directory
         run "pmc_$wl" 600 env OUT="gpurun_out/evidence_${TAG}_$wl/prof" KRE="$kre" \
-          BENCH="bench.py --workload $wl --steps 20 --warmup 3 --settle-ms 0 --no-cpu-baseline" bash scripts/profile.sh
+          BENCH="bench.py --full --workload $wl --steps 20 --warmup 3 --settle-ms 0 --no-cpu-baseline" bash scripts/profile.sh
       fi ;;
     ab:*) IFS=: read -r _ wl vars <<< "$step"
       run "ab_$wl" 600 env AB_WORKLOAD="$wl" AB_VARIANTS="$vars" python scripts/ab.py "gpurun_out/${TAG}_ab_$wl.json" ;;

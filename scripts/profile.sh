@@ -12,7 +12,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/prof}
 mkdir -p $OUT
-BENCH=${BENCH:-"bench.py --steps 20 --warmup 3 --no-cpu-baseline"}
+BENCH=${BENCH:-"bench.py --full --steps 20 --warmup 3 --no-cpu-baseline"}
 KRE=${KRE:-k_stream}
 run() {  # name, rocprof args...
   local name=$1; shift

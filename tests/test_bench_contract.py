@@ -234,7 +234,7 @@ def test_bench_self_launch_gloo_two_ranks_on_one_gpu():
     the one GPU: one line, n_gpus 2, both ranks' whole timed batches verified
     against the reference, shared_devices reported."""
     out = _bench(["--gpus", "2", "--steps", "5", "--warmup", "2", "--packets", "262144",
-                  "--settle-ms", "50"], {"LVLIP_DIST_BACKEND": "gloo"})
+                  "--settle-ms", "50", "--full"], {"LVLIP_DIST_BACKEND": "gloo"})
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -251,7 +251,7 @@ def test_bench_short_run_prints_contract_line():
     env = dict(os.environ)
     out = subprocess.run(
         [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2",
-         "--no-cpu-baseline"],
+         "--full", "--no-cpu-baseline"],
         cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -260,6 +260,88 @@ def test_bench_short_run_prints_contract_line():
     check_line(line, steps=5, warmup=2)
     assert line["config"]["bytes_per_gpu"] == TCP1500_BYTES
     assert line["roofline"]["frac"] > 0.5
+    # --full: the verification's record, the read probes and the PMC traffic
+    assert line["diag"]["verify"]["descriptors"] == 1_048_576
+    assert "read_probe_GBps" in line["diag"] and line["roofline"]["traffic"] > 0
+
+
+def test_bench_full_is_off_by_default():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (`--gpus 1 --steps K --warmup W`) times its K steps and
+    prints the line: no verification, CPU baseline, read probe or PMC lookup
+    (null / absent), the headline fields as ever.  With --dump-outputs it
+    writes the last timed step's checksums, which equal the oracle's over the
+    same (seeded) batch, so a second run writes the same file."""
+    import numpy as np
+    import pyoracle
+    import workloads
+
+    n = 70_001  # odd, several blocks; 105 MB of packets
+    d = tmp_path / "dump"
+    out = _bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--packets", str(n),
+                  "--dump-outputs", str(d)])
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    line = json.loads(lines[0])
+    assert line["metric"] == METRIC and line["unit"] == "GB/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "u16" and line["steps"] == 4 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(n * 1500 / (line["ms_per_step"] * 1e-3) / 1e9, rel=5e-3)
+    assert line["verified_bit_exact"] is None and line["cpu_baseline"] is None
+    assert "verify" not in line["diag"] and "read_probe_GBps" not in line["diag"]
+    assert line["roofline"]["traffic"] is None and line["roofline"]["traffic_source"] is None
+    assert line["roofline"]["kernel_ms"] > 0
+    assert sorted(os.listdir(d)) == ["checksums.npy"]
+    got = np.load(d / "checksums.npy")
+    assert got.dtype == np.float32 and got.shape == (n,)
+    b = workloads.make("tcp1500", n=n)
+    want = pyoracle.batch(b.host_bytes(), b.descs)
+    assert np.array_equal(got, want.astype(np.float32))
+    assert line["diag"]["dump_outputs"]["values"] == n
+
+
+def test_bench_dump_samples_a_large_output(tmp_path):
+    """Above its share of the 64 MB budget a rank writes a fixed seeded sample
+    and the sample's indices (the CPU side of --dump-outputs: no GPU needed)."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n = 1000
+    vals = (np.arange(n, dtype=np.uint32) * 65521 % 65536).astype(np.uint16)
+    out = torch.from_numpy(vals.view(np.int16).copy())
+    small = bench.dump_outputs(str(tmp_path / "a"), out, n, 0, 1)
+    assert small["files"] == ["checksums.npy"] and small["values"] == n
+    assert np.array_equal(np.load(tmp_path / "a" / "checksums.npy"), vals.astype(np.float32))
+    old = bench.DUMP_BYTES
+    bench.DUMP_BYTES = 2 * 12 * 100  # two ranks: 100 sampled values each
+    try:
+        first = None
+        for _rep in range(2):  # the same sample every time
+            r = bench.dump_outputs(str(tmp_path / "b"), out, n, 1, 2)
+            assert r["files"] == ["checksums_rank1.npy", "checksums_rank1_index.npy"] and r["values"] == 100
+            idx = np.load(tmp_path / "b" / "checksums_rank1_index.npy")
+            got = np.load(tmp_path / "b" / "checksums_rank1.npy")
+            assert idx.dtype == np.float64 and got.dtype == np.float32
+            assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+            assert np.array_equal(got, vals[idx.astype(np.int64)].astype(np.float32))
+            assert first is None or np.array_equal(first, idx)
+            first = idx
+    finally:
+        bench.DUMP_BYTES = old
 
 
 @pytest.mark.gpu
