@@ -235,6 +235,71 @@ int lvlip_icmp_echo_reply_dev(void *base, const lvlip_frame_desc *frames, uint32
 int lvlip_icmp_echo_reply_dev_ex(void *base, const lvlip_frame_desc *frames, uint32_t n,
                                  uint32_t flags, uint8_t *status, void *stream);
 
+/* ---- f2 on the device: segmentation ---------------------------------------- */
+
+/* tcp_send (src/tcp_output.c:445-478) cuts one write into ceil(len/mss)
+ * segments that differ only in seq, IP length, PSH, the two checksums and the
+ * payload slice.  For payload that already lives in HBM these calls do the
+ * same from one 54-byte header template, as a NIC's TSO does: payload copy and
+ * TCP checksum in one pass, finished Ethernet/IPv4/TCP frames out.
+ *
+ * A send is a payload range, an MSS and a template in network order: Ethernet
+ * 14 B, IPv4 with ihl 5, TCP with hl 5 (no options), holding the fields the
+ * first segment would carry; its IP length and both checksum fields are
+ * ignored.  Segment i of nseg = ceil(len/mss) carries dlen_i = min(mss,
+ * len - i*mss) payload bytes and is the 54 + dlen_i bytes at
+ * out + out_off + i*stride:
+ *   Ethernet  the template's 14 bytes
+ *   IPv4      the template, total length htons(40 + dlen_i), id as given (the
+ *             reference never advances it, src/ip_output.c:36), header
+ *             checksum checksum(ih, 20, 0) stored raw (src/ip_output.c:42,53)
+ *   TCP       the template, seq = htonl(seq0 + i*mss) mod 2^32; PSH and FIN of
+ *             the template on the last segment only (src/tcp_output.c:466);
+ *             csum = checksum(tcp, 20 + dlen_i, saddr + daddr + htons(6) +
+ *             htons(20 + dlen_i)) stored raw, the seed a u32 that wraps
+ *             (src/tcp.c:87-98: the carry is lost)
+ *   payload   bytes [i*mss, i*mss + dlen_i) of the send
+ * and, when fd is given, fd[seg0 + i] = {out_off + i*stride, 54 + dlen_i, 0},
+ * which the other _dev calls take as it is.  Nothing outside the frames is
+ * written (stride gaps keep their bytes); the payload is only read. */
+typedef struct lvlip_tso_send {
+    uint64_t payload_off;   /* from the payload base; any alignment            */
+    uint64_t out_off;       /* first frame, from the out base; any alignment   */
+    uint32_t len;           /* payload bytes, > 0                              */
+    uint32_t seg0;          /* index of this send's first segment in the call  */
+    uint32_t stride;        /* >= 54 + mss; any value                          */
+    uint16_t mss;           /* 1 .. 65495                                      */
+    uint16_t reserved;      /* 0                                               */
+    uint8_t  hdr[54];
+    uint8_t  pad[10];       /* 0; sizeof == 96                                 */
+} lvlip_tso_send;
+
+/* Host only: validates every send, fills seg0 with the running segment count
+ * and returns the total segment count (nseg of lvlip_tso_dev), or 0xFFFFFFFF
+ * for a malformed send (len or mss 0, mss > 65495, stride < 54 + mss, reserved
+ * != 0, ethertype != 0x0800, version/ihl != 0x45, protocol != 6, TCP header
+ * length != 5) or a total above LVLIP_MAX_BATCH.  *out_bytes (may be NULL) gets
+ * the largest out_off + (nseg-1)*stride + 54 + dlen_last: the bytes `out` must
+ * hold.  out_off is the caller's; the plan lays nothing out. */
+uint32_t lvlip_tso_plan(lvlip_tso_send *s, uint32_t n, uint64_t *out_bytes);
+
+/* The frames on the calling thread, one checksum() per field (the library's
+ * CPU code).  s as lvlip_tso_plan left it.  Returns 0, or LVLIP_EINVAL (NULL
+ * pointers with n > 0, a malformed or unplanned send) with nothing written.
+ * Reentrant; fd may be NULL. */
+int lvlip_tso_cpu(const void *payload, const lvlip_tso_send *s, uint32_t n, void *out,
+                  lvlip_frame_desc *fd);
+
+/* The same frames, bit for bit, in one launch on the caller's stream
+ * (asynchronous; no allocation, copy or synchronisation).  All pointers are
+ * device pointers, of any alignment for payload and out (s: 8 B, fd: 16 B);
+ * s as lvlip_tso_plan left it, nseg what it returned.  n == 0 is a no-op;
+ * NULL payload, s or out with n > 0, or nseg 0 or above LVLIP_MAX_BATCH, is
+ * LVLIP_EINVAL before any HIP call.  The device does not validate the
+ * templates again: the caller planned the sends. */
+int lvlip_tso_dev(const void *payload, const lvlip_tso_send *s, uint32_t n, uint32_t nseg,
+                  void *out, lvlip_frame_desc *fd, void *stream);
+
 /* RFC 1071 pseudo-header seed with the carries folded back (for RX verify of
  * checksums produced by RFC-correct peers). */
 uint32_t lvlip_pseudo_sum_rfc(uint32_t saddr, uint32_t daddr, uint8_t proto,

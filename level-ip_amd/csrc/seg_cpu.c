@@ -1,0 +1,138 @@
+/*
+ * seg_cpu.c — TCP segmentation from a header template (include/lvlip_skb.h,
+ * "f2 on the device: segmentation"): the plan, and the frames on the calling
+ * thread.  The device form (seg_kernels.hip) writes the same bytes.
+ *
+ * What tcp_send does per segment (src/tcp_output.c:445-478 ->
+ * tcp_transmit_skb, src/tcp_output.c:93-129 -> ip_output,
+ * src/ip_output.c:14-56), with the template standing for the socket's state.
+ */
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "lvlip_skb.h"
+
+#define TSO_HDR 54u       /* Ethernet 14 + IPv4 20 + TCP 20 */
+#define TSO_MSS_MAX 65495u /* 65535 - 40: the IPv4 total length is 16 bits */
+#define TCP_FIN_PSH 0x09u  /* byte 13 of the TCP header: FIN 0x01, PSH 0x08 */
+
+static inline uint32_t le32(const uint8_t *p)
+{
+    uint32_t v;
+    memcpy(&v, p, 4);
+    return v;
+}
+
+static inline uint32_t be32(const uint8_t *p)
+{
+    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+}
+
+static inline uint16_t bswap16(uint16_t x) { return (uint16_t)((x << 8) | (x >> 8)); }
+
+static int send_ok(const lvlip_tso_send *s)
+{
+    const uint8_t *h = s->hdr;
+    if (s->len == 0 || s->mss == 0 || s->mss > TSO_MSS_MAX || s->reserved != 0) return 0;
+    if (s->stride < TSO_HDR + s->mss) return 0;
+    if (h[12] != 0x08 || h[13] != 0x00) return 0; /* ethertype IPv4 */
+    if (h[14] != 0x45) return 0;                  /* version 4, ihl 5 */
+    if (h[23] != 6) return 0;                     /* IP_TCP */
+    if ((h[46] >> 4) != 5) return 0;              /* TCP header length, no options */
+    return 1;
+}
+
+static inline uint64_t send_segs(const lvlip_tso_send *s)
+{
+    return ((uint64_t)s->len + s->mss - 1u) / s->mss;
+}
+
+/* total segments, or 0xFFFFFFFF; with `planned`, seg0 must already be the
+ * running count */
+static uint32_t walk(const lvlip_tso_send *s, uint32_t n, int planned, uint64_t *out_bytes)
+{
+    uint64_t total = 0, top = 0;
+    for (uint32_t j = 0; j < n; j++) {
+        if (!send_ok(&s[j])) return 0xFFFFFFFFu;
+        if (planned && s[j].seg0 != total) return 0xFFFFFFFFu;
+        const uint64_t k = send_segs(&s[j]);
+        const uint64_t dlast = s[j].len - (k - 1u) * s[j].mss;
+        const uint64_t end = s[j].out_off + (k - 1u) * s[j].stride + TSO_HDR + dlast;
+        if (end > top) top = end;
+        total += k;
+        if (total > LVLIP_MAX_BATCH) return 0xFFFFFFFFu;
+    }
+    if (out_bytes) *out_bytes = top;
+    return (uint32_t)total;
+}
+
+uint32_t lvlip_tso_plan(lvlip_tso_send *s, uint32_t n, uint64_t *out_bytes)
+{
+    if (out_bytes) *out_bytes = 0;
+    if (n == 0) return 0;
+    if (!s) return 0xFFFFFFFFu;
+    const uint32_t total = walk(s, n, 0, out_bytes);
+    if (total == 0xFFFFFFFFu) {
+        if (out_bytes) *out_bytes = 0;
+        return total;
+    }
+    uint64_t run = 0;
+    for (uint32_t j = 0; j < n; j++) {
+        s[j].seg0 = (uint32_t)run;
+        run += send_segs(&s[j]);
+    }
+    return total;
+}
+
+int lvlip_tso_cpu(const void *payload, const lvlip_tso_send *s, uint32_t n, void *out,
+                  lvlip_frame_desc *fd)
+{
+    if (n == 0) return LVLIP_OK;
+    if (!payload || !s || !out) return LVLIP_EINVAL;
+    if (walk(s, n, 1, NULL) == 0xFFFFFFFFu) return LVLIP_EINVAL;
+    for (uint32_t j = 0; j < n; j++) {
+        const lvlip_tso_send *t = &s[j];
+        const uint8_t *src = (const uint8_t *)payload + t->payload_off;
+        const uint32_t seq0 = be32(t->hdr + 38);
+        const uint64_t k = send_segs(t);
+        for (uint64_t i = 0; i < k; i++) {
+            const uint64_t done = i * t->mss;
+            const uint32_t dlen = t->len - done < t->mss ? (uint32_t)(t->len - done) : t->mss;
+            const uint64_t off = t->out_off + i * t->stride;
+            uint8_t *f = (uint8_t *)out + off;
+            uint8_t *ih = f + 14, *th = f + 34;
+            memcpy(f, t->hdr, TSO_HDR);
+            memcpy(f + TSO_HDR, src + done, dlen);
+            /* ip_output: len, csum 0, then ip_send_check (src/ip_output.c:35,42,53) */
+            const uint16_t iplen = (uint16_t)(40u + dlen);
+            ih[2] = (uint8_t)(iplen >> 8);
+            ih[3] = (uint8_t)iplen;
+            ih[10] = ih[11] = 0;
+            const uint16_t ic = checksum(ih, 20, 0);
+            memcpy(ih + 10, &ic, 2);
+            /* tcp_transmit_skb: seq, csum 0, then tcp_v4_checksum
+             * (src/tcp_output.c:106,110,126); PSH on the last segment only
+             * (src/tcp_output.c:466), and FIN with it */
+            const uint32_t seq = seq0 + (uint32_t)done;
+            th[4] = (uint8_t)(seq >> 24);
+            th[5] = (uint8_t)(seq >> 16);
+            th[6] = (uint8_t)(seq >> 8);
+            th[7] = (uint8_t)seq;
+            if (i + 1u != k) th[13] &= (uint8_t)~TCP_FIN_PSH;
+            th[16] = th[17] = 0;
+            const uint16_t l4 = (uint16_t)(20u + dlen);
+            /* src/tcp.c:92-95: u32 adds, the carry out of bit 31 is lost */
+            const uint32_t seed = le32(ih + 12) + le32(ih + 16) + bswap16(6) + bswap16(l4);
+            const uint16_t tc = checksum(th, (int)l4, (int)seed);
+            memcpy(th + 16, &tc, 2);
+            if (fd) {
+                lvlip_frame_desc *d = &fd[t->seg0 + i];
+                d->offset = off;
+                d->len = TSO_HDR + dlen;
+                d->reserved = 0;
+            }
+        }
+    }
+    return LVLIP_OK;
+}

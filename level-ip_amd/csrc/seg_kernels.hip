@@ -1,0 +1,271 @@
+// seg_kernels.hip — TCP segmentation on the device (include/lvlip_skb.h, "f2 on
+// the device: segmentation"): payload in HBM + one 54-byte header template per
+// send -> finished Ethernet/IPv4/TCP frames, payload copy and TCP checksum in
+// one pass (one read, one write of every payload byte).  seg_cpu.c is the same
+// on the calling thread, bit for bit.
+//
+// Work mapping.  One DPP row (16 lanes) per segment, four segments per wave,
+// 16 per 256-thread workgroup; segment g -> send by a binary search over the
+// sends' seg0 (lvlip_tso_plan's running count).  A row sweeps its segment's
+// destination chunks 16 at a time, TSO_U sweeps (1 KiB of one frame) in flight
+// per row: a 590-B frame (MSS 536) is 38 chunks = one round at 59 % of the
+// lanes, a 1514-B frame two rounds' worth at 100 %, a 9000-B frame nine rounds;
+// a wave always has four frames' streams going.  The kernel cannot pick the
+// shape per send from the host (the sends are in device memory), so the row
+// is the one shape for every MSS.
+//
+// Alignment.  Everything is laid out by DESTINATION chunk: chunk k of a frame
+// at address F is the 16 aligned bytes at (F & ~15) + 16 k.  Its payload bytes
+// come from source address A = S + 16 k - (F & 15) - 54 onwards (S = the
+// segment's first payload byte), which is independent of F mod 16: the lane
+// loads the one or two aligned source chunks that hold them (never a chunk
+// without a byte of the segment's payload) and funnels bytes [A & 15,
+// (A & 15) + 16) out of the pair (v_alignbyte).  Whole chunks leave as 16-B
+// nontemporal stores (nobody on this XCD reads a frame again; `nt` keeps the
+// line policy streaming, MI355X store table); a frame's first and last chunk,
+// when the frame covers only part of them, leave as dword and byte stores of
+// exactly the frame's bytes, so a stride gap or an abutting neighbour frame is
+// never written.
+//
+// Checksum parity.  The reference sums the TCP segment's u16 words, which are
+// aligned to the TCP header: frame byte 34 + 2 w.  The funnelled data is
+// destination-aligned, so an aligned u16 holds one TCP word when F is even
+// and the high byte of one word with the low byte of the next when F is odd;
+// in the odd case the two bytes of every u16 are swapped before summing
+// (v_perm), which again adds every even-offset byte once and every odd-offset
+// byte times 256: the exact word sum W (mod 2^32), whatever the source's
+// alignment.  The fold happens once, on (seed + W) mod 2^32, as in
+// src/utils.c:46-54.
+//
+// The 54 header bytes are built in registers by every lane of the row from
+// the template (14 dwords), patched as tcp_transmit_skb and ip_output patch
+// them; the chunks that hold header bytes (the first 4 or 5) are kept back
+// until the row's sum is known and then leave with header and payload bytes
+// merged, one store per chunk.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdio.h>
+
+#include "csum_dev.h"
+
+namespace lvlip {
+
+constexpr uint32_t TSO_ROW = 16;                 // lanes per segment
+constexpr uint32_t TSO_SEGS = 256 / TSO_ROW;     // segments per workgroup
+constexpr int TSO_U = 4;                         // sweeps of a row in flight
+constexpr int TSO_HDR = 54;                      // Ethernet 14 + IPv4 20 + TCP 20
+
+// u32 sum over each 16-lane DPP row, left in every lane of the row
+// (quad_perm(1,0,3,2), quad_perm(2,3,0,1), row_ror:4, row_ror:8)
+__device__ __forceinline__ uint32_t row_sum_dpp(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0xF, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);
+    return v;
+}
+
+// bytes [sh, sh + 16) of the 32 bytes lo:hi, 0 <= sh <= 15
+__device__ __forceinline__ uint4 funnel16(const uint4 lo, const uint4 hi, uint32_t sh) {
+    const uint32_t q = sh >> 2, r = sh & 3u;
+    const uint32_t e0 = q == 0u ? lo.x : q == 1u ? lo.y : q == 2u ? lo.z : lo.w;
+    const uint32_t e1 = q == 0u ? lo.y : q == 1u ? lo.z : q == 2u ? lo.w : hi.x;
+    const uint32_t e2 = q == 0u ? lo.z : q == 1u ? lo.w : q == 2u ? hi.x : hi.y;
+    const uint32_t e3 = q == 0u ? lo.w : q == 1u ? hi.x : q == 2u ? hi.y : hi.z;
+    const uint32_t e4 = q == 0u ? hi.x : q == 1u ? hi.y : q == 2u ? hi.z : hi.w;
+    return make_uint4(__builtin_amdgcn_alignbyte(e1, e0, r), __builtin_amdgcn_alignbyte(e2, e1, r),
+                      __builtin_amdgcn_alignbyte(e3, e2, r), __builtin_amdgcn_alignbyte(e4, e3, r));
+}
+
+// word sum of a destination-aligned chunk, added to acc; sel swaps the bytes
+// of every u16 for frames at odd addresses
+__device__ __forceinline__ uint32_t chunk_acc(const uint4 v, uint32_t sel, uint32_t acc) {
+    acc = dot2_acc(__builtin_amdgcn_perm(v.x, v.x, sel), acc);
+    acc = dot2_acc(__builtin_amdgcn_perm(v.y, v.y, sel), acc);
+    acc = dot2_acc(__builtin_amdgcn_perm(v.z, v.z, sel), acc);
+    acc = dot2_acc(__builtin_amdgcn_perm(v.w, v.w, sel), acc);
+    return acc;
+}
+
+__device__ __forceinline__ uint32_t halves(uint32_t x) { return (x & 0xffffu) + (x >> 16); }
+
+__device__ __forceinline__ uint32_t bswap16u(uint32_t x) { return ((x & 0xffu) << 8) | ((x >> 8) & 0xffu); }
+
+// Bytes [b0, b1) of the chunk at the 16-B aligned address a: a whole chunk as
+// one nontemporal 16-B store, a partial one as the dwords and bytes inside the
+// range (plain vector stores), nothing outside it.
+__device__ __forceinline__ void store_chunk(uint64_t a, const uint4 v, int b0, int b1) {
+    typedef __attribute__((address_space(1))) u32x4 gvec;
+    typedef __attribute__((address_space(1))) uint32_t gdw;
+    typedef __attribute__((address_space(1))) uint8_t gby;
+    if (b0 <= 0 && b1 >= 16) {
+        __builtin_nontemporal_store(u32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<gvec*>(a));
+        return;
+    }
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const int s = min(max(b0 - 4 * d, 0), 4);
+        const int e = min(max(b1 - 4 * d, 0), 4);
+        if (s == 0 && e == 4) {
+            *reinterpret_cast<gdw*>(a + 4u * d) = w[d];
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (b >= s && b < e) *reinterpret_cast<gby*>(a + 4u * d + b) = (uint8_t)(w[d] >> (8 * b));
+        }
+    }
+}
+
+__device__ __forceinline__ uint4 pick(uint32_t j, const uint4 a, const uint4 b, const uint4 c,
+                                      const uint4 d) {
+    // block j of {zeros, a, b, c, d, zeros}; masks, not a select chain, which
+    // hipcc turns into a table in scratch
+    const uint32_t ma = j == 1u ? ~0u : 0u, mb = j == 2u ? ~0u : 0u;
+    const uint32_t mc = j == 3u ? ~0u : 0u, md = j == 4u ? ~0u : 0u;
+    return make_uint4((a.x & ma) | (b.x & mb) | (c.x & mc) | (d.x & md),
+                      (a.y & ma) | (b.y & mb) | (c.y & mc) | (d.y & md),
+                      (a.z & ma) | (b.z & mb) | (c.z & mc) | (d.z & md),
+                      (a.w & ma) | (b.w & mb) | (c.w & mc) | (d.w & md));
+}
+
+__global__ __launch_bounds__(256) void k_tso(const uint8_t* payload, const lvlip_tso_send* s, uint32_t n,
+                                             uint32_t nseg, uint8_t* out, lvlip_frame_desc* fd) {
+    const uint32_t tl = threadIdx.x & (TSO_ROW - 1u);
+    const uint64_t g64 = (uint64_t)blockIdx.x * TSO_SEGS + (threadIdx.x / TSO_ROW);
+    bool live = g64 < nseg;
+    const uint32_t g = live ? (uint32_t)g64 : 0u;
+
+    // the send of segment g: the last one whose seg0 is <= g (seg0 rises
+    // strictly: every send has a segment, and s[0].seg0 == 0)
+    uint32_t slo = 0, shi = n;
+    while (shi - slo > 1u) {
+        const uint32_t mid = slo + (shi - slo) / 2u;
+        if (s[mid].seg0 <= g) slo = mid;
+        else shi = mid;
+    }
+    const lvlip_tso_send* t = s + slo;
+    const uint32_t mss = t->mss, len = t->len;
+    const uint32_t i = g - t->seg0;
+    const uint64_t done = (uint64_t)i * mss;
+    live = live && g >= t->seg0 && done < len;  // a caller's nseg beyond the plan's: nothing to do
+    const uint32_t dlen = live ? (len - done < mss ? (uint32_t)(len - done) : mss) : 0u;
+    const bool last = done + dlen == len;
+
+    uint32_t h[14];
+    {
+        const uint32_t* hw = reinterpret_cast<const uint32_t*>(t->hdr);  // offset 32 of an 8-B aligned struct
+#pragma unroll
+        for (int k = 0; k < 14; ++k) h[k] = hw[k];
+    }
+
+    const uint64_t off = t->out_off + (uint64_t)i * t->stride;
+    const uint64_t F = reinterpret_cast<uint64_t>(out) + off;      // the frame's first byte
+    const uint64_t S = reinterpret_cast<uint64_t>(payload) + t->payload_off + done;
+    const int f = (int)(F & 15ull);
+    const uint64_t D = F - (uint64_t)f;                            // destination chunk 0
+    const int L = TSO_HDR + (int)dlen;
+    const uint32_t nch = live ? (uint32_t)(f + L + 15) >> 4 : 0u;  // chunks the frame touches
+    const uint32_t hk = (uint32_t)(f + TSO_HDR + 15) >> 4;         // of them with header bytes: 4 or 5
+    const uint32_t sel = (F & 1ull) ? 0x02030001u : 0x03020100u;
+
+    // ---- payload: copy and sum, destination chunk by destination chunk
+    uint32_t acc = 0;
+    uint4 keep = make_uint4(0u, 0u, 0u, 0u);  // the payload bytes of this lane's header chunk
+    for (uint32_t k0 = 0; k0 < nch; k0 += TSO_ROW * TSO_U) {
+        uint4 lo[TSO_U], hi[TSO_U];
+        int jlo[TSO_U], jhi[TSO_U];
+        uint32_t sh[TSO_U];
+#pragma unroll
+        for (int u = 0; u < TSO_U; ++u) {
+            const uint32_t k = k0 + (uint32_t)u * TSO_ROW + tl;
+            // chunk byte j is payload byte rel + j of the segment
+            const int rel = (int)(16u * k) - f - TSO_HDR;
+            jlo[u] = min(max(-rel, 0), 16);
+            jhi[u] = min(max((int)dlen - rel, 0), 16);
+            const bool has = k < nch && jlo[u] < jhi[u];
+            if (!has) jlo[u] = jhi[u] = 0;
+            const uint64_t A = S + (uint64_t)(int64_t)rel;
+            const uint64_t a0 = A & ~15ull;
+            sh[u] = (uint32_t)(A & 15ull);
+            // only source chunks that hold a payload byte of this segment
+            const bool need_lo = has && (int)sh[u] + jlo[u] < 16;
+            const bool need_hi = has && (int)sh[u] + jhi[u] > 16;
+            lo[u] = need_lo ? load_nt_global(a0) : make_uint4(0u, 0u, 0u, 0u);
+            hi[u] = need_hi ? load_nt_global(a0 + 16u) : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < TSO_U; ++u) {
+            const uint32_t k = k0 + (uint32_t)u * TSO_ROW + tl;
+            const uint4 v = mask_chunk(funnel16(lo[u], hi[u], sh[u]), jlo[u], jhi[u]);
+            acc = chunk_acc(v, sel, acc);
+            if (k < nch) {
+                if (k >= hk) store_chunk(D + 16ull * k, v, 0, min(16, f + L - (int)(16u * k)));
+                else keep = v;  // k = tl < hk <= 5: the first round's first sweep
+            }
+        }
+    }
+    const uint32_t W = row_sum_dpp(acc);  // the payload's word sum, in every lane of the row
+
+    // ---- the 54 header bytes (every lane of the row the same)
+    h[13] &= 0xffffu;                                             // bytes 52-53; the rest is the struct's pad
+    h[4] = (h[4] & 0xffff0000u) | bswap16u(40u + dlen);           // ip.len, src/ip_output.c:35,46
+    h[6] &= 0xffff0000u;                                          // ip.csum = 0, src/ip_output.c:42
+    const uint32_t ipw = (h[3] >> 16) + halves(h[4]) + halves(h[5]) + halves(h[6]) + halves(h[7]) +
+                         (h[8] & 0xffffu);
+    h[6] |= (uint32_t)finish(0u, ipw);                            // ip_send_check, src/ip_output.c:8-12
+    const uint32_t seq0 = __builtin_bswap32((h[9] >> 16) | (h[10] << 16));
+    const uint32_t seq = __builtin_bswap32(seq0 + (uint32_t)done);  // src/tcp_output.c:106,121
+    h[9] = (h[9] & 0xffffu) | (seq << 16);
+    h[10] = (h[10] & 0xffff0000u) | (seq >> 16);
+    if (!last) h[11] &= ~(0x09u << 24);                           // FIN, PSH: the last segment's
+    h[12] &= 0xffffu;                                             // tcp.csum = 0, src/tcp_output.c:110
+    const uint32_t thw = (h[8] >> 16) + halves(h[9]) + halves(h[10]) + halves(h[11]) + halves(h[12]) + h[13];
+    const uint32_t saddr = (h[6] >> 16) | (h[7] << 16), daddr = (h[7] >> 16) | (h[8] << 16);
+    // src/tcp.c:92-95: u32 adds, the carry out of bit 31 is lost
+    const uint32_t seed = saddr + daddr + 0x0600u + bswap16u(20u + dlen);
+    h[12] |= (uint32_t)finish(seed, thw + W) << 16;               // src/tcp_output.c:126
+
+    // ---- the chunks with header bytes: destination chunk k holds bytes
+    // [16 k + 16 - f, 16 k + 32 - f) of {16 zero bytes, the header, zeros}
+    if (tl < hk && tl < nch) {
+        const uint4 b1 = make_uint4(h[0], h[1], h[2], h[3]), b2 = make_uint4(h[4], h[5], h[6], h[7]);
+        const uint4 b3 = make_uint4(h[8], h[9], h[10], h[11]), b4 = make_uint4(h[12], h[13], 0u, 0u);
+        const uint4 nx = pick(tl + 1u, b1, b2, b3, b4);
+        const uint4 cu = f == 0 ? nx : pick(tl, b1, b2, b3, b4);
+        const uint4 hv = funnel16(cu, nx, (uint32_t)(16 - f) & 15u);
+        const uint4 v = make_uint4(keep.x | hv.x, keep.y | hv.y, keep.z | hv.z, keep.w | hv.w);
+        store_chunk(D + 16ull * tl, v, tl == 0u ? f : 0, min(16, f + L - (int)(16u * tl)));
+    }
+    if (fd && live && tl == 0u) {
+        typedef __attribute__((address_space(1))) u32x4 gvec;
+        *reinterpret_cast<gvec*>(reinterpret_cast<uint64_t>(fd + g)) =
+            u32x4{(uint32_t)off, (uint32_t)(off >> 32), (uint32_t)L, 0u};
+    }
+}
+
+}  // namespace lvlip
+
+extern "C" {
+
+void lvlip_set_last_hip_error(const char* msg);  // csum_kernels.hip (hidden)
+
+int lvlip_tso_dev(const void* payload, const lvlip_tso_send* s, uint32_t n, uint32_t nseg, void* out,
+                  lvlip_frame_desc* fd, void* stream) {
+    if (n == 0) return LVLIP_OK;
+    if (!payload || !s || !out || nseg == 0 || nseg > LVLIP_MAX_BATCH) return LVLIP_EINVAL;
+    const uint32_t grid = (uint32_t)(((uint64_t)nseg + lvlip::TSO_SEGS - 1u) / lvlip::TSO_SEGS);
+    hipLaunchKernelGGL(lvlip::k_tso, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)payload, s,
+                       n, nseg, (uint8_t*)out, fd);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "k_tso: %s", hipGetErrorString(e));
+        lvlip_set_last_hip_error(msg);
+        return LVLIP_EHIP;
+    }
+    return LVLIP_OK;
+}
+
+}  // extern "C"

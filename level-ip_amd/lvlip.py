@@ -242,6 +242,12 @@ SIGNATURES = {
     "lvlip_rx_verify_skb_list_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                                     ctypes.c_uint32]),
     "lvlip_tx_checksum_skb_list_cpu": (ctypes.c_int, [ctypes.c_void_p]),
+    # f2 on the device: segmentation (seg_cpu.c, seg_kernels.hip)
+    "lvlip_tso_plan": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),
+    "lvlip_tso_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                     ctypes.c_void_p]),
+    "lvlip_tso_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "lvlip_auto_kernel": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (ctypes.c_char_p, []),
@@ -542,6 +548,73 @@ def icmp_echo_reply_dev(base, fdescs, stream=None, flags: int = 0):
                                                s.cuda_stream)
     _check(rc, "lvlip_icmp_echo_reply_dev")
     return status[:n]
+
+
+# ------------------------------------------- f2 on the device: segmentation --
+
+# struct lvlip_tso_send (include/lvlip_skb.h), 96 B
+TsoSend = np.dtype([("payload_off", "<u8"), ("out_off", "<u8"), ("len", "<u4"), ("seg0", "<u4"),
+                    ("stride", "<u4"), ("mss", "<u2"), ("reserved", "<u2"), ("hdr", "u1", (54,)),
+                    ("pad", "u1", (10,))])
+assert TsoSend.itemsize == 96
+TSO_HDR = 54
+
+
+def tso_send(hdr, payload_off: int, length: int, mss: int, out_off: int = 0, stride: int = 0) -> np.ndarray:
+    """One TsoSend record; stride 0 means frames that abut (54 + mss)."""
+    r = np.zeros(1, dtype=TsoSend)
+    r["payload_off"], r["out_off"], r["len"], r["mss"] = payload_off, out_off, length, mss
+    r["stride"] = stride or TSO_HDR + mss
+    r["hdr"][0] = np.frombuffer(bytes(hdr), dtype=np.uint8)
+    return r
+
+
+def tso_plan(sends: np.ndarray):
+    """lvlip_tso_plan: validates the sends and fills their seg0 in place.
+    Returns (nseg, out_bytes); ValueError for a malformed send or too many
+    segments."""
+    if sends.dtype != TsoSend or not sends.flags.c_contiguous or not sends.flags.writeable:
+        raise TypeError("sends: a writeable contiguous TsoSend array")
+    out_bytes = ctypes.c_uint64(0)
+    nseg = int(_lib.lvlip_tso_plan(sends.ctypes.data if sends.size else None, sends.size,
+                                   ctypes.byref(out_bytes)))
+    if nseg == PLAN_MALFORMED:
+        raise ValueError("malformed send (or more than LVLIP_MAX_BATCH segments)")
+    return nseg, int(out_bytes.value)
+
+
+def tso_cpu(payload, sends: np.ndarray, out: Optional[np.ndarray] = None):
+    """lvlip_tso_cpu: plans the sends and builds their frames on the calling
+    thread.  Returns (out, fd): the frame buffer (a new zeroed one of the plan's
+    out_bytes unless `out` is given, which then keeps its bytes outside the
+    frames) and the FRAME_DESC_DTYPE descriptors."""
+    nseg, out_bytes = tso_plan(sends)
+    pay = _as_u8(payload)
+    if any(int(s["payload_off"]) + int(s["len"]) > pay.size for s in sends):
+        raise ValueError("a send reads past the payload")
+    if out is None:
+        out = np.zeros(out_bytes, dtype=np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < out_bytes:
+        raise ValueError("out: a contiguous uint8 array of at least the plan's out_bytes")
+    fd = np.zeros(nseg, dtype=FRAME_DESC_DTYPE)
+    _check(_lib.lvlip_tso_cpu(pay.ctypes.data, sends.ctypes.data, sends.size, out.ctypes.data,
+                              fd.ctypes.data), "lvlip_tso_cpu")
+    return out, fd
+
+
+def tso_dev(payload_t, sends_t, nseg: int, out_t, fd_t=None, stream=None):
+    """lvlip_tso_dev on CUDA uint8 tensors: payload_t the payload, sends_t the
+    planned TsoSend records' bytes (96 each), out_t the frame buffer (at least
+    the plan's out_bytes), fd_t (optional) 16 bytes per segment for the frame
+    descriptors.  One launch on `stream` (default: current), asynchronous."""
+    import torch
+
+    n = sends_t.numel() * sends_t.element_size() // TsoSend.itemsize
+    s = stream or torch.cuda.current_stream(out_t.device)
+    if fd_t is not None and fd_t.numel() * fd_t.element_size() < 16 * nseg:
+        raise ValueError("fd_t: 16 bytes per segment")
+    _check(_lib.lvlip_tso_dev(payload_t.data_ptr(), sends_t.data_ptr(), n, nseg, out_t.data_ptr(),
+                              fd_t.data_ptr() if fd_t is not None else None, s.cuda_stream), "lvlip_tso_dev")
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
