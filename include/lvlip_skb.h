@@ -94,7 +94,10 @@ void lvlip_rx_apply(uint32_t n, uint8_t *verdict, uint32_t m, const uint32_t *ta
  * untouched on error): LVLIP_EINVAL for a malformed frame (not IPv4, ihl < 5,
  * shorter than 14 + its IP length), LVLIP_ERANGE for a frame longer than the
  * context's arena.  A call of at most the context's cpu_max frames runs on the
- * calling thread, with the same results and codes. */
+ * calling thread, with the same results and codes.
+ * Each frame may be listed once per call.  A frame listed twice is
+ * unsupported: its fields may be stored from two threads at once, and after a
+ * failed call it need not get back the bytes it held before the call. */
 int lvlip_tx_checksum(lvlip_csum_ctx *ctx, lvlip_frame *frames, uint32_t n);
 
 /* Plan: fills iov[]/field[] (capacity 2n; field = where each result goes),

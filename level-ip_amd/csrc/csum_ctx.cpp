@@ -99,17 +99,6 @@ int h2d_ordered(lvlip_csum_ctx* c, Slot& s, void* dst, const void* src, size_t n
     return LVLIP_OK;
 }
 
-int finish_pieces(lvlip_csum_ctx* c, int rc) {
-    for (auto& s : c->slot) {
-        const int r2 = drain(c, s);
-        if (rc == LVLIP_OK) rc = r2;
-    }
-    if (rc != LVLIP_OK)
-        for (auto& s : c->slot) (void)hipStreamSynchronize(s.stream);
-    c->last_copy = nullptr;  // the next call's first piece waits for nothing
-    return rc;
-}
-
 const Region* find_region(const lvlip_csum_ctx* c, const void* p, uint64_t len) {
     const uint8_t* a = (const uint8_t*)p;
     for (const Region& r : c->regions)
@@ -122,6 +111,13 @@ const Region* find_region(const lvlip_csum_ctx* c, const void* p, uint64_t len) 
 namespace {
 
 using namespace lvlip_ctx;
+
+// An environment variable as a number clamped to [lo, hi]; dflt when unset.
+long long env_ll(const char* name, long long dflt, long long lo, long long hi) {
+    const char* e = getenv(name);
+    const long long v = e ? atoll(e) : dflt;
+    return v < lo ? lo : v > hi ? hi : v;
+}
 
 void free_slot(Slot& s) {
     if (s.h_bytes) (void)hipHostFree(s.h_bytes);
@@ -136,14 +132,10 @@ void free_slot(Slot& s) {
     s = Slot{};
 }
 
-// Copy a piece to the device, checksum it, copy results back.  The bytes come
-// from `src` (the slot's pinned arena, or a registered region: DMA straight
-// from it), or, when `dev_base` is set, are read by the kernel in place
-// (zero-copy: `bytes` is then only the length hint's numerator).
-int launch_piece(lvlip_csum_ctx* c, Slot& s, uint64_t bytes, uint32_t count, uint16_t* user_out,
-                 const uint8_t* src = nullptr, const uint8_t* dev_base = nullptr) {
-    hipError_t e;
-    if (const int rc = count_piece(c, bytes); rc != LVLIP_OK) return rc;
+// A packet piece through the device (launch_piece): count checksums of 2 B
+// each, the bytes' H2D ordered behind the previous piece's.
+int launch_packets(lvlip_csum_ctx* c, Slot& s, uint64_t bytes, uint32_t count, uint16_t* user_out,
+                   const uint8_t* src = nullptr, const uint8_t* dev_base = nullptr) {
     lvlip_launch_cfg cfg{};
     cfg.kernel = LVLIP_KERNEL_AUTO;  // the piece's average length picks the kernel
     cfg.len_hint = (int32_t)(bytes / count > 0x7fffffffull ? 0x7fffffff : bytes / count);
@@ -154,32 +146,10 @@ int launch_piece(lvlip_csum_ctx* c, Slot& s, uint64_t bytes, uint32_t count, uin
         cfg.kernel = LVLIP_KERNEL_FLAT;
         cfg.unroll = 8;
     }
-    if (bytes <= c->direct_max && (dev_base || !src || src == s.h_bytes)) {
-        // A small piece: the copies' fixed costs (an SDMA round trip each way)
-        // outweigh moving the bytes, so the kernel reads the pinned arena (or
-        // the zero-copy region) and the descriptors over PCIe and writes the
-        // results straight into the pinned result buffer.
-        const int rc = lvlip_csum_batch_dev_ex(dev_base ? dev_base : s.dh_bytes, s.dh_desc, count,
-                                               s.dh_out, s.stream, &cfg);
-        if (rc != LVLIP_OK) return rc;
-        return arm_slot(c, s, user_out, (size_t)count * sizeof(uint16_t), bytes);
-    }
-    // the descriptors first: the bytes' copy may wait for the previous piece's
-    if ((e = hipMemcpyAsync(s.d_desc, s.h_desc, (size_t)count * sizeof(lvlip_csum_desc),
-                            hipMemcpyHostToDevice, s.stream)) != hipSuccess)
-        return fail(c, e, "H2D descriptors");
-    if (!dev_base) {
-        const uint64_t nb = src && src != s.h_bytes ? bytes : align16(bytes);
-        const int rc = h2d_ordered(c, s, s.d_bytes, src ? src : s.h_bytes, nb, "H2D bytes");
-        if (rc != LVLIP_OK) return rc;
-    }
-    int rc = lvlip_csum_batch_dev_ex(dev_base ? dev_base : s.d_bytes, s.d_desc, count, s.d_out,
-                                     s.stream, &cfg);
-    if (rc != LVLIP_OK) return rc;
-    if ((e = hipMemcpyAsync(s.h_out, s.d_out, (size_t)count * sizeof(uint16_t),
-                            hipMemcpyDeviceToHost, s.stream)) != hipSuccess)
-        return fail(c, e, "D2H results");
-    return arm_slot(c, s, user_out, (size_t)count * sizeof(uint16_t), bytes);
+    return launch_piece(c, s, bytes, count, sizeof(uint16_t), true, user_out, src, dev_base,
+                        [&](const uint8_t* base, const lvlip_csum_desc* d, uint16_t* out) {
+                            return lvlip_csum_batch_dev_ex(base, d, count, out, s.stream, &cfg);
+                        });
 }
 
 // The code of the first item (in batch order) that `check` refuses, or
@@ -204,18 +174,6 @@ int first_failure(lvlip_csum_ctx* c, uint32_t n, const F& check) {
     return f == ~0ull ? LVLIP_OK : -(int)(f & 0xffu);
 }
 
-// The context's scratch array for the host batch calls, at least `bytes`
-// (kept across calls: fresh pages would fault on every call; trim_scratch
-// releases one above kScratchKeep when the call ends).
-void* host_scratch(lvlip_csum_ctx* c, size_t bytes) {
-    if (c->host_scratch_bytes < bytes) {
-        free(c->host_scratch);
-        c->host_scratch = malloc(bytes);
-        c->host_scratch_bytes = c->host_scratch ? bytes : 0;
-    }
-    return c->host_scratch;
-}
-
 // The packets of a host call on the calling thread (cpu_max): Group 1's
 // checksum() per packet, the reference's own arithmetic (src/utils.c:40-55).
 template <class Ptr, class Len, class Seed>
@@ -230,40 +188,35 @@ int cpu_batch(lvlip_csum_ctx* c, uint32_t n, uint16_t* out, const Ptr& ptr_of, c
 }
 
 // Gathers n packets (ptr_of, len_of, seed_of) into the pinned arena, each at
-// the next 16-B aligned offset, piece by piece over the two slots (the
-// scattered path of lvlip_csum_batch_host, and the flat call's path for
-// descriptors that do not cover their span densely in order).  Every packet
-// fits the arena (checked by the callers).
+// the next 16-B aligned offset, piece by piece (the scattered path of
+// lvlip_csum_batch_host, and the flat call's path for descriptors that do not
+// cover their span densely in order).
 template <class Ptr, class Len, class Seed>
 int gather_batch(lvlip_csum_ctx* c, uint32_t n, uint16_t* out, const Ptr& ptr_of, const Len& len_of,
                  const Seed& seed_of) {
-    int cur = 0;
-    uint32_t i = 0;
-    int rc = LVLIP_OK;
-    while (i < n && rc == LVLIP_OK) {
-        Slot& s = c->slot[cur];
-        if ((rc = drain(c, s)) != LVLIP_OK) break;
-        // lay out a piece: packet k at the next 16-B aligned offset ...
-        uint64_t off = 0;
-        uint32_t k = 0;
-        const uint32_t first = i;
-        while (i < n && k < c->max_desc) {
-            const int32_t len = len_of(i);
-            const uint64_t need = len > 0 ? (uint64_t)len : 0;
-            if (off + need > (k ? c->piece : c->arena)) break;
-            s.h_desc[k].offset = off;
-            s.h_desc[k].len = len;
-            s.h_desc[k].start_sum = seed_of(i);
-            off = align16(off + need);
-            ++k;
-            ++i;
-        }
-        // ... then gather the bytes, packets split over the host threads,
-        // nontemporal stores (copy_nt), the next packets prefetched
-        {
+    NoDone cb;
+    return run_pieces(
+        c, n,
+        // lay out a piece: packet k at the next 16-B aligned offset, up to the
+        // piece size (a larger packet alone, up to the arena).  The offsets
+        // are a running sum, so the cut writes the descriptors as it goes ...
+        [&](Slot& s, uint32_t first, uint32_t) {
+            Cut p;
+            for (uint32_t i = first; i < n && p.k < c->max_desc; ++i, ++p.k) {
+                const int32_t len = len_of(i);
+                const uint64_t need = len > 0 ? (uint64_t)len : 0;
+                if (p.bytes + need > (p.k ? c->piece : c->arena)) break;
+                s.h_desc[p.k] = lvlip_csum_desc{p.bytes, len, seed_of(i)};
+                p.bytes = align16(p.bytes + need);
+            }
+            return p;
+        },
+        // ... then the bytes are gathered, packets split over the host
+        // threads, nontemporal stores (copy_nt), the next packets prefetched
+        [&](Slot& s, uint32_t first, const Cut& p) {
             uint8_t* dst = s.h_bytes;
             const lvlip_csum_desc* hd = s.h_desc;
-            parallel_ranges(c, k, 1024, [=](uint64_t lo, uint64_t hi) {
+            parallel_ranges(c, p.k, 1024, [=](uint64_t lo, uint64_t hi) {
                 for (uint64_t q = lo; q < hi; ++q) {
                     if (q + 8 < hi && hd[q + 8].len > 0)
                         for (int32_t l = 0; l < hd[q + 8].len; l += 64)
@@ -273,17 +226,17 @@ int gather_batch(lvlip_csum_ctx* c, uint32_t n, uint16_t* out, const Ptr& ptr_of
                 }
                 _mm_sfence();
             });
-        }
-        rc = launch_piece(c, s, off ? off : 16, k, out + first);
-        cur ^= 1;
-    }
-    return finish_pieces(c, rc);
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
+            return launch_packets(c, s, p.bytes ? p.bytes : 16, p.k, out + first);
+        },
+        cb);
 }
 
 // Zero-copy: descriptors only (offsets from the region's first byte rounded
-// down to 16), kernel reads the registered pages in place.  `offset_of(i)`
+// down to 16), kernel reads the registered pages in place.  `addr_of(i)`
 // gives packet i's byte address; the whole batch lies in region `r`.  Pieces
-// of at most c->piece bytes (the descriptors of the next piece are written,
+// of at most an arena's bytes (the descriptors of the next piece are written,
 // on the pool threads, while the kernel reads the previous one's packets;
 // a piece was max_desc descriptors before, for a 1M-packet batch one piece
 // whose 16 MB of descriptors were written before the kernel started).
@@ -292,56 +245,63 @@ int zerocopy_batch(lvlip_csum_ctx* c, const Region& r, uint32_t n, uint16_t* out
                    DescOf desc_of, LenOf len_of) {
     const uint8_t* h0 = (const uint8_t*)((uintptr_t)r.host & ~(uintptr_t)15);
     const uint8_t* d0 = r.dev - (r.host - h0);
-    int cur = 0;
-    uint32_t i = 0;
-    int rc = LVLIP_OK;
-    while (i < n && rc == LVLIP_OK) {
-        Slot& s = c->slot[cur];
-        if ((rc = drain(c, s)) != LVLIP_OK) break;
-        const uint32_t first = i;
-        uint32_t k = 0;
-        uint64_t bytes = 0;
-        while (i < n && k < c->max_desc) {
-            const int32_t l = len_of(i);
-            const uint64_t need = l > 0 ? (uint64_t)l : 0u;
-            if (k && bytes + need > c->arena) break;
-            bytes += need;
-            ++k;
-            ++i;
-        }
-        lvlip_csum_desc* hd = s.h_desc;
-        parallel_ranges(c, k, 16384, [&, hd, first](uint64_t lo, uint64_t hi) {
-            for (uint64_t q = lo; q < hi; ++q) {
-                lvlip_csum_desc dq = desc_of(first + (uint32_t)q);
-                dq.offset = (uint64_t)((const uint8_t*)addr_of(first + (uint32_t)q) - h0);
-                hd[q] = dq;
+    NoDone cb;
+    return run_pieces(
+        c, n,
+        [&](Slot&, uint32_t first, uint32_t) {
+            Cut p;  // nothing is moved: any packet may start a piece
+            for (uint32_t i = first; i < n && p.k < c->max_desc; ++i, ++p.k) {
+                const int32_t l = len_of(i);
+                const uint64_t need = l > 0 ? (uint64_t)l : 0u;
+                if (p.k && p.bytes + need > c->arena) break;
+                p.bytes += need;
             }
-        });
-        rc = launch_piece(c, s, bytes ? bytes : 16, k, out + first, nullptr, d0);
-        cur ^= 1;
-    }
-    return finish_pieces(c, rc);
+            return p;
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
+            lvlip_csum_desc* hd = s.h_desc;
+            parallel_ranges(c, p.k, 16384, [&, hd, first](uint64_t lo, uint64_t hi) {
+                for (uint64_t q = lo; q < hi; ++q) {
+                    lvlip_csum_desc dq = desc_of(first + (uint32_t)q);
+                    dq.offset = (uint64_t)((const uint8_t*)addr_of(first + (uint32_t)q) - h0);
+                    hd[q] = dq;
+                }
+            });
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
+            return launch_packets(c, s, p.bytes ? p.bytes : 16, p.k, out + first, nullptr, d0);
+        },
+        cb);
 }
 
-// lvlip_csum_batch_host_flat's GPU path over validated descriptors.  dense:
-// 1 / 0 when the caller has scanned the batch (dense_ordered's rule), -1 to
-// scan here.  Dense batches move their spans (the copy engine straight from a
-// registered region, else one nontemporal copy per span into the pinned
-// arena); other batches are read in place from a zero-copy region, or
-// gathered packet by packet.
+// Whether a packet's 16-B span fits the arena: what the paths that move spans
+// (host_flat_impl's dense path) need of every packet.
+inline bool span_fits(const lvlip_csum_ctx* c, uint64_t offset, int32_t len) {
+    return align16(offset + (len > 0 ? (uint64_t)len : 0u)) - (offset & ~15ull) <= c->arena;
+}
+
+// lvlip_csum_batch_host_flat's GPU path over validated descriptors (every
+// packet span_fits).  dense: 1 / 0 when the caller has scanned the batch
+// (span_dense), -1 to scan here.  Dense batches move their spans (the copy
+// engine straight from a registered region, else one nontemporal copy per
+// span into the pinned arena); other batches are read in place from a
+// zero-copy region, or gathered packet by packet.
 int host_flat_impl(lvlip_csum_ctx* c, const uint8_t* b, size_t base_bytes, const lvlip_csum_desc* d, uint32_t n,
                    uint16_t* out, int dense) {
     const Region* reg = c->regions.empty() ? nullptr : find_region(c, b, base_bytes);
-    if (dense < 0)
-        dense = dense_ordered(
-            c, n, [b, d](uint32_t q) { return (uint64_t)(uintptr_t)(b + d[q].offset); },
-            [d](uint32_t q) { return d[q].len; });
+    if (dense < 0) {
+        SpanScan sc;
+        span_scan(c, n, 4096, &sc, [b, d](uint32_t q, SpanScan& s) {
+            if (d[q].len > 0) span_add(s, (uint64_t)(uintptr_t)(b + d[q].offset), (uint64_t)d[q].len);
+            return true;
+        });
+        dense = span_dense(sc, c->span_ratio);
+    }
     if (!dense) {
         if (reg && (reg->flags & LVLIP_REG_ZEROCOPY))
             return zerocopy_batch(
                 c, *reg, n, out, [&](uint32_t q) { return b + d[q].offset; }, [&](uint32_t q) { return d[q]; },
                 [&](uint32_t q) { return d[q].len; });
-        // every packet fits the arena: the flat call's rule is the stricter
         return gather_batch(
             c, n, out, [b, d](uint32_t q) { return b + d[q].offset; }, [d](uint32_t q) { return d[q].len; },
             [d](uint32_t q) { return d[q].start_sum; });
@@ -352,63 +312,59 @@ int host_flat_impl(lvlip_csum_ctx* c, const uint8_t* b, size_t base_bytes, const
     // a zero-copy region moves its spans as from a DMA region (tcp1500:
     // 54.6-55.2 against 52.5 GB/s in place)
     const uint64_t limit = reg ? c->arena : c->piece;
-    int cur = 0;
-    uint32_t i = 0;
-    int rc = LVLIP_OK;
-    while (i < n && rc == LVLIP_OK) {
-        Slot& s = c->slot[cur];
-        if ((rc = drain(c, s)) != LVLIP_OK) break;
+    NoDone cb;
+    return run_pieces(
+        c, n,
         // A piece is a run of descriptors whose byte span [lo16, hi) fits the
-        // arena.  The span is copied with one memcpy, keeping each packet's
-        // offset mod 16 (so odd/unaligned starts stay exactly as given).
-        const uint32_t first = i;
-        uint64_t lo16 = ~0ull, hi = 0;
-        uint32_t k = 0;
-        while (i < n && k < c->max_desc) {
-            const uint64_t o = d[i].offset;
-            const uint64_t e = o + (d[i].len > 0 ? (uint64_t)d[i].len : 0);
-            const uint64_t nlo = (o & ~15ull) < lo16 ? (o & ~15ull) : lo16;
-            const uint64_t nhi = e > hi ? e : hi;
-            // k >= 1 here: a single span always fits the arena (checked by the caller)
-            if (align16(nhi) - nlo > (k ? limit : c->arena)) break;
-            lo16 = nlo;
-            hi = nhi;
-            ++k;
-            ++i;
-        }
-        const uint64_t span = hi > lo16 ? hi - lo16 : 0;
-        const uint8_t* from = nullptr;
-        if (span && reg) {
-            // f3 DMA: the copy engine reads the registered span directly.  Its
-            // last bytes up to the next 16 B may lie past base_bytes, so copy
-            // exactly `span` and let the kernel's 16-B tail read the arena.
-            from = b + lo16;
-        } else if (span) {
-            // the span in 64-B blocks over the threads, nontemporal stores
-            uint8_t* dst = s.h_bytes;
-            const uint8_t* src = b + lo16;
-            const uint64_t nblk = (span + 63) / 64;
-            parallel_ranges(c, nblk, 8192, [=](uint64_t lo, uint64_t hi) {
-                const uint64_t e = hi * 64 < span ? hi * 64 : span;
-                copy_nt(dst + lo * 64, src + lo * 64, e - lo * 64);
-                _mm_sfence();
-            });
-        }
-        {
+        // limit (a single larger span alone, up to the arena).  The span is
+        // moved whole, keeping each packet's offset mod 16 (so odd/unaligned
+        // starts stay exactly as given).
+        [&](Slot&, uint32_t first, uint32_t) {
+            Cut p;
+            uint64_t lo16 = ~0ull, hi = 0;
+            for (uint32_t i = first; i < n && p.k < c->max_desc; ++i, ++p.k) {
+                const uint64_t o = d[i].offset;
+                const uint64_t e = o + (d[i].len > 0 ? (uint64_t)d[i].len : 0);
+                const uint64_t nlo = (o & ~15ull) < lo16 ? (o & ~15ull) : lo16;
+                const uint64_t nhi = e > hi ? e : hi;
+                if (align16(nhi) - nlo > (p.k ? limit : c->arena)) break;
+                lo16 = nlo;
+                hi = nhi;
+            }
+            p.lo = lo16;
+            p.bytes = hi > lo16 ? hi - lo16 : 0;
+            return p;
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
+            if (p.bytes && !reg) {
+                // the span in 64-B blocks over the threads, nontemporal stores
+                uint8_t* dst = s.h_bytes;
+                const uint8_t* src = b + p.lo;
+                const uint64_t span = p.bytes, nblk = (span + 63) / 64;
+                parallel_ranges(c, nblk, 8192, [=](uint64_t lo, uint64_t hi) {
+                    const uint64_t e = hi * 64 < span ? hi * 64 : span;
+                    copy_nt(dst + lo * 64, src + lo * 64, e - lo * 64);
+                    _mm_sfence();
+                });
+            }
             lvlip_csum_desc* hd = s.h_desc;
             const lvlip_csum_desc* src = d + first;
-            const uint64_t base16 = lo16;
-            parallel_ranges(c, k, 16384, [hd, src, base16](uint64_t lo, uint64_t hi) {
+            const uint64_t base16 = p.lo;
+            parallel_ranges(c, p.k, 16384, [hd, src, base16](uint64_t lo, uint64_t hi) {
                 for (uint64_t q = lo; q < hi; ++q) {
                     hd[q] = src[q];
                     hd[q].offset = src[q].offset - base16;
                 }
             });
-        }
-        rc = launch_piece(c, s, span ? span : 16, k, out + first, from);
-        cur ^= 1;
-    }
-    return finish_pieces(c, rc);
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
+            // f3 DMA: the copy engine reads the registered span directly.  Its
+            // last bytes up to the next 16 B may lie past base_bytes, so copy
+            // exactly the span and let the kernel's 16-B tail read the arena.
+            return launch_packets(c, s, p.bytes ? p.bytes : 16, p.k, out + first,
+                                  p.bytes && reg ? b + p.lo : nullptr);
+        },
+        cb);
 }
 
 }  // namespace
@@ -429,78 +385,44 @@ int lvlip_csum_ctx_create(lvlip_csum_ctx** out, int device, size_t arena_bytes) 
     if (!c) return LVLIP_ENOMEM;
     c->device = device;
     c->arena = arena_bytes;
-    {
-        const char* e = getenv("LVLIP_GATHER_THREADS");
-        const unsigned hw = std::thread::hardware_concurrency();
-        int t = e ? atoi(e) : (int)(hw ? (hw < 16 ? hw : 16) : 1);
-        c->threads = t < 1 ? 1 : (t > 64 ? 64 : t);
-    }
+    const long long kU32 = 0xffffffffll, kMax = 0x7fffffffffffffffll;
+    const unsigned hw = std::thread::hardware_concurrency();
+    c->threads = (int)env_ll("LVLIP_GATHER_THREADS", hw ? (hw < 16 ? hw : 16) : 1, 1, 64);
     // LVLIP_DIRECT_MAX: pieces of at most this many bytes skip the H2D/D2H
     // copies (launch_piece); 0 turns that off
-    {
-        const char* e = getenv("LVLIP_DIRECT_MAX");
-        const long long v = e ? atoll(e) : (long long)kDirectMax;
-        c->direct_max = v > 0 ? (uint64_t)v : 0u;
-    }
+    c->direct_max = (uint64_t)env_ll("LVLIP_DIRECT_MAX", (long long)kDirectMax, 0, kMax);
     // LVLIP_PIECE_MAX: bytes per piece, so that even a batch of a few MB is cut
     // into pieces whose gather, copies and kernel overlap across the two slots
-    {
-        const char* e = getenv("LVLIP_PIECE_MAX");
-        const long long v = e ? atoll(e) : (long long)kPieceMax;
-        const uint64_t pm = v > 0 ? align16((uint64_t)v) : arena_bytes;
-        c->piece = pm < arena_bytes ? pm : arena_bytes;
-    }
+    // (0, or more than the arena: the arena)
+    const uint64_t pm = (uint64_t)env_ll("LVLIP_PIECE_MAX", (long long)kPieceMax, 0, (long long)arena_bytes);
+    c->piece = pm ? align16(pm) : arena_bytes;
     // LVLIP_FIRST_PIECE: the host frame calls' first piece, in bytes; later
     // pieces double up to the piece size (0 or unset: 4 MiB; a value >= the
-    // piece size turns the ramp off)
-    {
-        const char* e = getenv("LVLIP_FIRST_PIECE");
-        const long long v = e ? atoll(e) : 0;
-        c->first_piece = v > 0 ? align16((uint64_t)v) : (4ull << 20);
-        if (c->first_piece > c->piece) c->first_piece = c->piece;  // the ramp's shifts never overflow
-    }
+    // piece size turns the ramp off).  At most the piece size: the ramp's
+    // shifts never overflow
+    const uint64_t fp = (uint64_t)env_ll("LVLIP_FIRST_PIECE", 0, 0, (long long)c->piece);
+    c->first_piece = fp ? align16(fp) : (4ull << 20);
+    if (c->first_piece > c->piece) c->first_piece = c->piece;
     // LVLIP_INLINE_MAX: host calls of at most this many packets / frames keep
     // their host steps on the calling thread (ctx_impl.h; 0: never)
-    {
-        const char* e = getenv("LVLIP_INLINE_MAX");
-        const long long v = e ? atoll(e) : 32768;
-        c->inline_max = v > 0 ? (uint32_t)(v > 0xffffffffll ? 0xffffffffll : v) : 0u;
-    }
+    c->inline_max = (uint32_t)env_ll("LVLIP_INLINE_MAX", 32768, 0, kU32);
     // LVLIP_SPAN_RATIO (1-64): the density rule's span-to-bytes ratio (span_dense)
-    {
-        const char* e = getenv("LVLIP_SPAN_RATIO");
-        const long long v = e ? atoll(e) : 2;
-        c->span_ratio = (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v);
-    }
+    c->span_ratio = (uint32_t)env_ll("LVLIP_SPAN_RATIO", 2, 1, 64);
     // LVLIP_CPU_MAX: host calls of at most this many packets / frames run on
     // the calling thread (lvlip_csum_ctx_set_cpu_max; 0: always the GPU)
-    {
-        const char* e = getenv("LVLIP_CPU_MAX");
-        const long long v = e ? atoll(e) : (long long)LVLIP_CPU_MAX_DEFAULT;
-        c->cpu_max = v > 0 ? (uint32_t)(v > 0xffffffffll ? 0xffffffffll : v) : 0u;
-    }
-    {
-        const char* e = getenv("LVLIP_FAIL_PIECE");
-        const long long v = e ? atoll(e) : 0;
-        c->fail_piece = v > 0 ? (uint32_t)(v > 0xffffffffll ? 0xffffffffll : v) : 0u;
-    }
+    c->cpu_max = (uint32_t)env_ll("LVLIP_CPU_MAX", LVLIP_CPU_MAX_DEFAULT, 0, kU32);
+    // LVLIP_FAIL_PIECE: the error paths' test hook (ctx_impl.h), never set in production
+    c->fail_piece = (uint32_t)env_ll("LVLIP_FAIL_PIECE", 0, 0, kU32);
+    if (c->fail_piece)
+        fprintf(stderr, "lvlip_csum: LVLIP_FAIL_PIECE=%u is set (a test hook): piece %u of every GPU call will fail\n",
+                c->fail_piece, c->fail_piece);
     // LVLIP_BLOCK_MIN: a piece of at least this many bytes is waited for by
     // polling between short sleeps instead of by spinning: the pipeline's
     // other slot keeps the GPU busy meanwhile, so the late wake-up costs no
     // throughput and the waiting thread little CPU (0: always spin)
-    {
-        const char* e = getenv("LVLIP_BLOCK_MIN");
-        const long long v = e ? atoll(e) : (long long)kBlockMin;
-        c->block_min = v > 0 ? (uint64_t)v : 0u;
-    }
-    {
-        const char* e = getenv("LVLIP_COPY_ORDER");
-        c->copy_order = e ? atoi(e) != 0 : 1;
-    }
-    {
-        const char* e = getenv("LVLIP_FRAME_TRACE");
-        c->frame_trace = e && *e == '1';
-    }
+    c->block_min = (uint64_t)env_ll("LVLIP_BLOCK_MIN", (long long)kBlockMin, 0, kMax);
+    c->copy_order = env_ll("LVLIP_COPY_ORDER", 1, -kMax, kMax) != 0;
+    c->frame_trace = env_ll("LVLIP_FRAME_TRACE", 0, 0, kMax) == 1;
     // descriptors per piece: one per 64 B of arena (a piece of smaller packets
     // simply ends at this count; the next piece takes the rest)
     c->max_desc = (uint32_t)(arena_bytes / 64 < 4096 ? 4096 : arena_bytes / 64);
@@ -534,9 +456,7 @@ int lvlip_csum_ctx_create(lvlip_csum_ctx** out, int device, size_t arena_bytes) 
     // Each slot copies `warm` bytes of its arena each way once
     // (LVLIP_WARM_BYTES, default 1 MiB; 0 skips it).
     {
-        size_t warm = 1u << 20;
-        if (const char* e = getenv("LVLIP_WARM_BYTES")) warm = strtoull(e, nullptr, 10);
-        if (warm > arena_bytes) warm = arena_bytes;
+        const size_t warm = (size_t)env_ll("LVLIP_WARM_BYTES", 1 << 20, 0, (long long)arena_bytes);
         hipError_t e = hipSuccess;
         for (auto& s : c->slot) {
             if (!warm || e != hipSuccess) break;
@@ -649,7 +569,7 @@ int lvlip_csum_batch_host(lvlip_csum_ctx* c, const lvlip_csum_iov* pkts, uint32_
     if (n <= c->cpu_max) return cpu_batch(c, n, out, ptr_of, len_of, seed_of);
     DeviceGuard g(c->device);
     begin_gpu_call(c);
-    int rc = LVLIP_ERANGE;  // "not handled by a region path yet"
+    int rc = 1;  // no code of the library's: not taken by a region path yet
     if (!c->regions.empty()) {
         // f3: all packets inside one registered region (the region of the
         // first non-empty packet; regions never overlap) -> no gather at all:
@@ -662,40 +582,32 @@ int lvlip_csum_batch_host(lvlip_csum_ctx* c, const lvlip_csum_iov* pkts, uint32_
         const Region* r = i0 < n ? find_region(c, pkts[i0].ptr, (uint64_t)pkts[i0].len) : nullptr;
         if (r) {
             // one pass on the pool threads: every packet inside r, the
-            // packets' span, bytes and jumps (dense_ordered's scan), and
-            // their flat descriptors relative to r (written whether or not
-            // they are used; the array is trimmed after a huge call)
-            lvlip_csum_desc* fd = (lvlip_csum_desc*)host_scratch(c, sizeof(lvlip_csum_desc) * (size_t)n);
+            // packets' span, bytes and jumps, whether each one's 16-B span
+            // fits the arena (the flat call's rule), and their flat
+            // descriptors relative to r (written whether or not they are
+            // used; the array is trimmed after a huge call)
+            lvlip_csum_desc* fd = (lvlip_csum_desc*)scratch(c->host_scratch, c->host_scratch_bytes,
+                                                            sizeof(lvlip_csum_desc) * (size_t)n);
             const uint8_t *r0 = r->host, *r1 = r->host + r->bytes;
-            std::atomic<bool> outside{false};
-            constexpr uint32_t kParts = 256;
-            SpanScan part[kParts];
-            const uint32_t np = n / 4096u < 1u ? 1u : (n / 4096u > kParts ? kParts : n / 4096u);
-            parallel_ranges(c, np, 1, [&, fd, r0, r1](uint64_t plo, uint64_t phi) {
-                for (uint64_t j = plo; j < phi; ++j) {
-                    SpanScan sc;
-                    const uint32_t a = (uint32_t)((uint64_t)n * j / np), z = (uint32_t)((uint64_t)n * (j + 1) / np);
-                    for (uint32_t q = a; q < z; ++q) {
-                        const int32_t len = pkts[q].len;
-                        uint64_t o = 0;
-                        if (len > 0) {
-                            const uint8_t* p = (const uint8_t*)pkts[q].ptr;
-                            if (p < r0 || p + len > r1) {
-                                outside.store(true, std::memory_order_relaxed);
-                                return;
-                            }
-                            o = (uint64_t)(p - r0);
-                            span_add(sc, o, (uint64_t)len);
-                        }
-                        if (fd) fd[q] = lvlip_csum_desc{o, len, pkts[q].start_sum};
-                    }
-                    part[j] = sc;
+            std::atomic<bool> unfit{false};
+            SpanScan sc;
+            const bool inside = span_scan(c, n, 4096, &sc, [&, fd, r0, r1](uint32_t q, SpanScan& s) {
+                const int32_t len = pkts[q].len;
+                uint64_t o = 0;
+                if (len > 0) {
+                    const uint8_t* p = (const uint8_t*)pkts[q].ptr;
+                    if (p < r0 || p + len > r1) return false;
+                    o = (uint64_t)(p - r0);
+                    span_add(s, o, (uint64_t)len);
+                    if (!span_fits(c, o, len)) unfit.store(true, std::memory_order_relaxed);
                 }
+                if (fd) fd[q] = lvlip_csum_desc{o, len, pkts[q].start_sum};
+                return true;
             });
-            const bool inside = !outside.load();
-            if (inside && fd && span_dense(span_merge(part, np), c->span_ratio))
-                // refused only when one packet's 16-B span exceeds the arena
-                // (the flat call's rule): then the gather below takes it
+            // a packet whose 16-B span exceeds the arena cannot move as a
+            // span: the batch is then read in place or gathered, where a
+            // packet needs only its own bytes rounded up to 16 (checked above)
+            if (inside && fd && !unfit.load(std::memory_order_relaxed) && span_dense(sc, c->span_ratio))
                 rc = host_flat_impl(c, r->host, r->bytes, fd, n, out, 1);
             else if (inside && (r->flags & LVLIP_REG_ZEROCOPY))
                 rc = zerocopy_batch(
@@ -709,7 +621,7 @@ int lvlip_csum_batch_host(lvlip_csum_ctx* c, const lvlip_csum_iov* pkts, uint32_
                     [&](uint32_t q) { return pkts[q].len; });
         }
     }
-    if (rc == LVLIP_ERANGE) rc = gather_batch(c, n, out, ptr_of, len_of, seed_of);
+    if (rc > 0) rc = gather_batch(c, n, out, ptr_of, len_of, seed_of);
     trim_scratch(c);
     return rc;
 }
@@ -720,14 +632,11 @@ int lvlip_csum_batch_host_flat(lvlip_csum_ctx* c, const void* base, size_t base_
     if (n == 0) return LVLIP_OK;
     begin_call(c, n);
     const uint8_t* b = (const uint8_t*)base;
-    const uint64_t arena = c->arena;
-    const int bad = first_failure(c, n, [d, base_bytes, arena](uint32_t q) {
-        const uint64_t e = d[q].offset + (d[q].len > 0 ? (uint64_t)d[q].len : 0u);
-        if (e > base_bytes) return LVLIP_EINVAL;
+    const int bad = first_failure(c, n, [c, d, base_bytes](uint32_t q) {
+        if (d[q].offset + (d[q].len > 0 ? (uint64_t)d[q].len : 0u) > base_bytes) return LVLIP_EINVAL;
         // a single packet whose 16-B span exceeds the arena: refuse before any
         // piece is in flight (a piece still in flight would later write into out[])
-        if (align16(e) - (d[q].offset & ~15ull) > arena) return LVLIP_ERANGE;
-        return LVLIP_OK;
+        return span_fits(c, d[q].offset, d[q].len) ? LVLIP_OK : LVLIP_ERANGE;
     });
     if (bad != LVLIP_OK) return bad;
     if (n <= c->cpu_max)

@@ -19,6 +19,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
+#include <chrono>
 #include <vector>
 
 #include "gather_pool.h"
@@ -67,6 +69,19 @@ struct Region {
     uint32_t flags = 0;
 };
 
+// LVLIP_FRAME_TRACE=1 (read when the context is made): one line per frame
+// call on stderr with the host's time in each step (diagnostics for the
+// pipeline's balance; off by default, and off outside the frame calls).
+struct Trace {
+    bool on = false;
+    std::chrono::steady_clock::time_point t0;
+    double pass1 = 0, gather = 0, wait = 0, apply = 0;
+    uint32_t pieces = 0;
+    static double ms(std::chrono::steady_clock::time_point a) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+    }
+};
+
 }  // namespace lvlip_ctx
 
 struct lvlip_csum_ctx {
@@ -94,6 +109,7 @@ struct lvlip_csum_ctx {
     void* host_scratch = nullptr;
     size_t host_scratch_bytes = 0;
     int frame_trace = 0;      // LVLIP_FRAME_TRACE=1: per-step host times on stderr
+    lvlip_ctx::Trace trace;   // the current frame call's
     // host calls of at most this many packets / frames run on the calling
     // thread (lvlip_csum_ctx_set_cpu_max; 0: never)
     uint32_t cpu_max = LVLIP_CPU_MAX_DEFAULT;
@@ -131,9 +147,6 @@ int fail(lvlip_csum_ctx* c, hipError_t e, const char* what, int code = LVLIP_EHI
 int h2d_ordered(lvlip_csum_ctx* c, Slot& s, void* dst, const void* src, size_t n, const char* what);
 // Waits for a slot's in-flight piece and copies its results to user_out.
 int drain(lvlip_csum_ctx* c, Slot& s);
-// End of a batch call: drains both slots; after a failure also waits for what
-// a half-enqueued piece left on the slot streams.
-int finish_pieces(lvlip_csum_ctx* c, int rc);
 // The registered region holding [p, p + len), or nullptr.
 const Region* find_region(const lvlip_csum_ctx* c, const void* p, uint64_t len);
 // Marks the slot busy with a piece whose results (out_bytes) go to user_out.
@@ -157,6 +170,15 @@ inline void begin_gpu_call(lvlip_csum_ctx* c) {
 // that one huge batch does not hold memory for the context's lifetime
 // (the iov call's 16 n bytes of flat descriptors).
 constexpr size_t kScratchKeep = 64ull << 20;
+// One of the context's scratch arrays (p, its size b), grown to at least `need`.
+inline void* scratch(void*& p, size_t& b, size_t need) {
+    if (b < need) {
+        free(p);
+        p = malloc(need);
+        b = p ? need : 0;
+    }
+    return p;
+}
 inline void trim_scratch(lvlip_csum_ctx* c) {
     auto trim = [](void*& p, size_t& b) {
         if (b > kScratchKeep) {
@@ -176,7 +198,7 @@ inline void trim_scratch(lvlip_csum_ctx* c) {
 // addresses summing to at most twice the span plus 1 MiB.  Pieces are runs in
 // call order cut at the piece size, so a shuffled batch over a large buffer
 // would cut into pieces of one or two items, each moving a whole span (ADVICE
-// r05).  A scan is kept per part of the batch (pool threads), then merged in
+// r05).  A scan is kept per part of the batch (span_scan), then merged in
 // part order.
 struct SpanScan {
     uint64_t lo = ~0ull, hi = 0, sum = 0, jumps = 0;
@@ -277,26 +299,146 @@ void parallel_ranges(lvlip_csum_ctx* c, uint64_t n, uint64_t min_per_thread, F f
     c->pool.run((int)t, [&](int k) { fn(n * (uint64_t)k / t, n * (uint64_t)(k + 1) / t); });
 }
 
-// span_dense over n items (start address addr_of(q), length len_of(q); items
-// of length <= 0 skipped), scanned in parts of at least 4096 items (at most
-// 256 parts) on the pool threads.
-template <class Addr, class Len>
-bool dense_ordered(lvlip_csum_ctx* c, uint32_t n, const Addr& addr_of, const Len& len_of) {
+// The span scan of n items on the pool threads: item(q, scan) adds item q to
+// its part's scan (span_add) or leaves it out, and returns false to veto the
+// whole batch (an item outside the region, or one that does not fit).  Parts
+// of at least min_part items, at most 256, merged in call order into *out.
+// False when an item vetoed.
+template <class Item>
+bool span_scan(lvlip_csum_ctx* c, uint32_t n, uint32_t min_part, SpanScan* out, const Item& item) {
     constexpr uint32_t kParts = 256;
     SpanScan part[kParts];
-    const uint32_t np = n / 4096u < 1u ? 1u : (n / 4096u > kParts ? kParts : n / 4096u);
+    std::atomic<bool> veto{false};
+    const uint32_t np = n / min_part < 1u ? 1u : (n / min_part > kParts ? kParts : n / min_part);
     parallel_ranges(c, np, 1, [&](uint64_t plo, uint64_t phi) {
         for (uint64_t j = plo; j < phi; ++j) {
             SpanScan s;
             const uint32_t a = (uint32_t)((uint64_t)n * j / np), b = (uint32_t)((uint64_t)n * (j + 1) / np);
-            for (uint32_t q = a; q < b; ++q) {
-                const int64_t l = (int64_t)len_of(q);
-                if (l > 0) span_add(s, (uint64_t)addr_of(q), (uint64_t)l);
-            }
+            for (uint32_t q = a; q < b; ++q)
+                if (!item(q, s)) {
+                    veto.store(true, std::memory_order_relaxed);
+                    return;
+                }
             part[j] = s;
         }
     });
-    return span_dense(span_merge(part, np), c->span_ratio);
+    if (veto.load(std::memory_order_relaxed)) return false;
+    *out = span_merge(part, np);
+    return true;
+}
+
+// One piece of `count` items (descriptors in the slot's pinned h_desc) through
+// the device step, results of out_item bytes each to user_out when the slot
+// drains.  The bytes come from the slot's pinned arena, from `src` (a
+// registered region: DMA straight from it), or, when `dev_base` is set, are
+// read by the kernel in place (zero-copy: `bytes` then only counts).  A piece
+// of at most direct_max bytes skips the copies: their fixed costs (an SDMA
+// round trip each way) outweigh moving the bytes, so the kernel reads the
+// pinned arena (or the zero-copy region) and the descriptors over PCIe and
+// writes its results into the pinned result buffer.  Otherwise, on the slot's
+// stream: the descriptors (first: the bytes' copy may wait for the previous
+// piece's), the bytes, the kernel, the results.  ordered: the bytes go through
+// h2d_ordered (the packet calls); the frame calls do not order their pieces'
+// copies behind each other: in one process that cost the registered-slab
+// calls 1.5-3 % and tripled their host CPU time per frame.
+// step(base, desc, out): the device step on s.stream.
+template <class Step>
+int launch_piece(lvlip_csum_ctx* c, Slot& s, uint64_t bytes, uint32_t count, size_t out_item, bool ordered,
+                 void* user_out, const uint8_t* src, const uint8_t* dev_base, const Step& step) {
+    static_assert(sizeof(lvlip_csum_desc) == sizeof(lvlip_frame_desc), "one descriptor array for both");
+    hipError_t e;
+    int rc = count_piece(c, bytes);
+    if (rc != LVLIP_OK) return rc;
+    const size_t nout = (size_t)count * out_item;
+    if (bytes <= c->direct_max && (dev_base || !src)) {
+        if ((rc = step(dev_base ? dev_base : s.dh_bytes, s.dh_desc, s.dh_out)) != LVLIP_OK) return rc;
+        return arm_slot(c, s, user_out, nout, bytes);
+    }
+    if ((e = hipMemcpyAsync(s.d_desc, s.h_desc, (size_t)count * sizeof(lvlip_csum_desc), hipMemcpyHostToDevice,
+                            s.stream)) != hipSuccess)
+        return fail(c, e, "H2D descriptors");
+    if (!dev_base) {
+        // a region's span ends at its last byte; the arena's is rounded up for the kernel's 16-B tail
+        const uint8_t* from = src ? src : s.h_bytes;
+        const uint64_t nb = src ? bytes : align16(bytes);
+        if (ordered)
+            rc = h2d_ordered(c, s, s.d_bytes, from, nb, "H2D bytes");
+        else if ((e = hipMemcpyAsync(s.d_bytes, from, nb, hipMemcpyHostToDevice, s.stream)) != hipSuccess)
+            rc = fail(c, e, "H2D bytes");
+        if (rc != LVLIP_OK) return rc;
+    }
+    if ((rc = step(dev_base ? dev_base : s.d_bytes, s.d_desc, s.d_out)) != LVLIP_OK) return rc;
+    if ((e = hipMemcpyAsync(s.h_out, s.d_out, nout, hipMemcpyDeviceToHost, s.stream)) != hipSuccess)
+        return fail(c, e, "D2H results");
+    return arm_slot(c, s, user_out, nout, bytes);
+}
+
+// What a path's cut returns for the piece that starts at item `first`: k items
+// (at least one, or an error code), and what its fill and launch need: the
+// piece's bytes (gathered, read in place, or its span's) and, for a span, its
+// first byte.
+struct Cut {
+    uint32_t k = 0;
+    uint64_t bytes = 0;
+    uint64_t lo = 0;
+    int rc = LVLIP_OK;
+};
+// No per-piece callback.
+struct NoDone {
+    void done(uint32_t, uint32_t) {}
+    bool stop() const { return false; }
+};
+
+// Every host batch path: n items cut into pieces, double-buffered over the
+// two slots (piece k is cut and filled on the CPU while piece k-1's copies and
+// kernel run on the other slot's stream).  Per piece, on the slot s it runs on:
+//   cut(s, first, idx)   the piece number idx, from item `first`: a Cut.  k == 0
+//                        without an error is LVLIP_ERANGE (an item no piece can
+//                        hold); such a piece is never launched
+//   fill(s, first, cut)  the slot's descriptors, and its bytes when the path gathers
+//   launch(s, first, cut) the device step (launch_piece)
+// cb.done(first, k) is called once a piece's results are in the caller's
+// array, pieces in order (TX applies them while later pieces run); after
+// cb.stop() no further piece is issued.  Ends with both slots drained, the
+// older piece first; after a failure also waits for what a half-enqueued
+// piece left on the slot streams.
+template <class CutF, class Fill, class Launch, class Done>
+int run_pieces(lvlip_csum_ctx* c, uint32_t n, const CutF& cut, const Fill& fill, const Launch& launch, Done& cb) {
+    using clock = std::chrono::steady_clock;
+    uint32_t first[kSlots] = {}, count[kSlots] = {};
+    Trace& tr = c->trace;
+    auto drain_slot = [&](int j) {
+        Slot& s = c->slot[j];
+        if (!s.busy) return (int)LVLIP_OK;
+        clock::time_point t;
+        if (tr.on) t = clock::now();
+        const int rc = drain(c, s);
+        if (tr.on) tr.wait += Trace::ms(t), t = clock::now();
+        if (rc == LVLIP_OK) cb.done(first[j], count[j]);
+        if (tr.on) tr.apply += Trace::ms(t), tr.pieces++;
+        return rc;
+    };
+    int cur = 0, rc = LVLIP_OK;
+    uint32_t idx = 0;
+    for (uint32_t i = 0; i < n && rc == LVLIP_OK; cur ^= 1) {
+        Slot& s = c->slot[cur];
+        if ((rc = drain_slot(cur)) != LVLIP_OK || cb.stop()) break;
+        const Cut p = cut(s, i, idx++);
+        if ((rc = p.rc != LVLIP_OK ? p.rc : p.k ? LVLIP_OK : LVLIP_ERANGE) != LVLIP_OK) break;
+        fill(s, i, p);
+        first[cur] = i;
+        count[cur] = p.k;
+        rc = launch(s, i, p);
+        i += p.k;
+    }
+    for (int j = 0; j < kSlots; ++j) {
+        const int r2 = drain_slot((cur + j) % kSlots);
+        if (rc == LVLIP_OK) rc = r2;
+    }
+    if (rc != LVLIP_OK)
+        for (auto& s : c->slot) (void)hipStreamSynchronize(s.stream);
+    c->last_copy = nullptr;  // the next call's first piece waits for nothing
+    return rc;
 }
 
 }  // namespace lvlip_ctx

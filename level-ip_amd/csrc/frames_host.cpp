@@ -73,27 +73,6 @@ inline uint32_t need_len(int mode, const lvlip_frame& f) {
     return f.len;
 }
 
-// The context's scratch array of at least `bytes` (kept for later calls).
-void* scratch(lvlip_csum_ctx* c, size_t bytes) {
-    if (c->frame_scratch_bytes < bytes) {
-        free(c->frame_scratch);
-        c->frame_scratch = malloc(bytes);
-        c->frame_scratch_bytes = c->frame_scratch ? bytes : 0;
-    }
-    return c->frame_scratch;
-}
-
-// A second scratch array (the gather's prefix sums and RX + L4's lengths),
-// kept like the first.
-void* scratch2(lvlip_csum_ctx* c, size_t bytes) {
-    if (c->frame_scratch2_bytes < bytes) {
-        free(c->frame_scratch2);
-        c->frame_scratch2 = malloc(bytes);
-        c->frame_scratch2_bytes = c->frame_scratch2 ? bytes : 0;
-    }
-    return c->frame_scratch2;
-}
-
 // Frames per piece: the slot's descriptor array and its result buffer.
 inline uint32_t frames_per_piece(const lvlip_csum_ctx* c, int mode) {
     const uint64_t by_out = (uint64_t)c->max_desc * sizeof(uint16_t) / out_bytes(mode);
@@ -111,93 +90,14 @@ inline uint64_t piece_bytes(const lvlip_csum_ctx* c, uint32_t idx) {
     return idx < 16 && c->first_piece <= (c->piece >> idx) ? c->first_piece << idx : c->piece;
 }
 
-// LVLIP_FRAME_TRACE=1 (read when the context is made): one line per call on
-// stderr with the host's time in each step (diagnostics for the pipeline's
-// balance; off by default).
-struct Trace {
-    bool on = false;
-    std::chrono::steady_clock::time_point t0;
-    double pass1 = 0, gather = 0, wait = 0, apply = 0;
-    uint32_t pieces = 0;
-    static double ms(std::chrono::steady_clock::time_point a) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-    }
-};
-thread_local Trace g_trace;
-
-// Called with each piece's frame range once its results are in the caller's
-// array (TX: the host applies that piece's records while later pieces run).
-struct PieceDone {
-    virtual void done(uint32_t first, uint32_t k) = 0;
-    // no further piece is worth issuing (TX: a malformed frame was seen, the
-    // call will undo and fail)
-    virtual bool stop() const { return false; }
-};
-
-// drain() plus the piece callback; the slot remembers its piece's range.
-struct FrameSlots {
-    lvlip_csum_ctx* c;
-    PieceDone* cb;
-    uint32_t first[kSlots] = {0, 0}, count[kSlots] = {0, 0};
-    int drain_slot(int k) {
-        Slot& s = c->slot[k];
-        const bool was = s.busy;
-        auto t = std::chrono::steady_clock::now();
-        const int rc = drain(c, s);
-        if (g_trace.on) g_trace.wait += Trace::ms(t);
-        t = std::chrono::steady_clock::now();
-        if (rc == LVLIP_OK && was && cb) cb->done(first[k], count[k]);
-        if (g_trace.on && was) g_trace.apply += Trace::ms(t), g_trace.pieces++;
-        return rc;
-    }
-    // finish_pieces with the callback: the older piece first
-    int finish(int rc, int next) {
-        for (int j = 0; j < kSlots; ++j) {
-            const int r2 = drain_slot((next + j) % kSlots);
-            if (rc == LVLIP_OK) rc = r2;
-        }
-        if (rc != LVLIP_OK)
-            for (auto& s : c->slot) (void)hipStreamSynchronize(s.stream);
-        return rc;
-    }
-};
-
-// One piece of k frames (descriptors in the slot's pinned h_desc) through the
-// device step, as csum_ctx.cpp's launch_piece: the frames come from the
-// slot's pinned arena, from `src` (a registered region: DMA), or are read in
-// place at `dev_base` (zero-copy).  A piece of at most direct_max bytes skips
-// the copies: the kernel reads the arena (or region) and the descriptors over
-// PCIe and writes its results into the pinned result buffer.
-int launch_frame_piece(lvlip_csum_ctx* c, Slot& s, int mode, uint64_t bytes, uint32_t k, void* user_out,
-                       const uint8_t* src = nullptr, const uint8_t* dev_base = nullptr) {
-    hipError_t e;
-    if (const int rc = count_piece(c, bytes); rc != LVLIP_OK) return rc;
-    const size_t nout = (size_t)k * out_bytes(mode);
-    if (bytes <= c->direct_max && (dev_base || !src)) {
-        const int rc = lvlip_frames_host_launch(mode, dev_base ? dev_base : s.dh_bytes,
-                                                (const lvlip_frame_desc*)s.dh_desc, k, s.dh_out, s.stream);
-        if (rc != LVLIP_OK) return rc;
-        return arm_slot(c, s, user_out, nout, bytes);
-    }
-    // the descriptors, then the frames, on the slot's stream.  The frame calls
-    // do not order their pieces' copies behind each other (h2d_ordered): in
-    // one process that cost the registered-slab calls 1.5-3 % and tripled
-    // their host CPU time per frame
-    if ((e = hipMemcpyAsync(s.d_desc, s.h_desc, (size_t)k * sizeof(lvlip_frame_desc), hipMemcpyHostToDevice,
-                            s.stream)) != hipSuccess)
-        return fail(c, e, "H2D frame descriptors");
-    if (!dev_base) {
-        const uint64_t nb = src ? bytes : align16(bytes);
-        if ((e = hipMemcpyAsync(s.d_bytes, src ? src : s.h_bytes, nb, hipMemcpyHostToDevice, s.stream)) !=
-            hipSuccess)
-            return fail(c, e, "H2D frames");
-    }
-    const int rc = lvlip_frames_host_launch(mode, dev_base ? dev_base : s.d_bytes,
-                                            (const lvlip_frame_desc*)s.d_desc, k, s.d_out, s.stream);
-    if (rc != LVLIP_OK) return rc;
-    if ((e = hipMemcpyAsync(s.h_out, s.d_out, nout, hipMemcpyDeviceToHost, s.stream)) != hipSuccess)
-        return fail(c, e, "D2H frame results");
-    return arm_slot(c, s, user_out, nout, bytes);
+// One piece of k frames through the device step (launch_piece): records or
+// verdicts of out_bytes(mode) each, the bytes' H2D not ordered.
+int launch_frames(lvlip_csum_ctx* c, Slot& s, int mode, uint64_t bytes, uint32_t k, void* user_out,
+                  const uint8_t* src = nullptr, const uint8_t* dev_base = nullptr) {
+    return launch_piece(c, s, bytes, k, out_bytes(mode), false, user_out, src, dev_base,
+                        [&](const uint8_t* base, const lvlip_csum_desc* d, uint16_t* out) {
+                            return lvlip_frames_host_launch(mode, base, (const lvlip_frame_desc*)d, k, out, s.stream);
+                        });
 }
 
 // Scattered frames: each frame's need_len bytes (len[i] when given) copied
@@ -205,34 +105,32 @@ int launch_frame_piece(lvlip_csum_ctx* c, Slot& s, int mode, uint64_t bytes, uin
 // slot offset in the batch's virtual arena stream (pre[n] the total), so a
 // piece is the run of frames whose slots fit the piece, found by binary
 // search, and the pool threads write its descriptors as they copy.
+template <class Done>
 int frames_gather(lvlip_csum_ctx* c, const lvlip_frame* fr, uint32_t n, int mode, uint8_t* out,
-                  const uint32_t* len, const uint64_t* pre, PieceDone* cb) {
+                  const uint32_t* len, const uint64_t* pre, Done& cb) {
     const uint32_t fmax = frames_per_piece(c, mode), ob = out_bytes(mode);
-    FrameSlots fs{c, cb};
-    int cur = 0;
-    uint32_t i = 0, idx = 0;
-    int rc = LVLIP_OK;
-    while (i < n && rc == LVLIP_OK) {
-        Slot& s = c->slot[cur];
-        if ((rc = fs.drain_slot(cur)) != LVLIP_OK) break;
-        if (cb && cb->stop()) break;
-        lvlip_frame_desc* hd = (lvlip_frame_desc*)s.h_desc;
-        const uint32_t first = i;
-        const uint64_t pb = piece_bytes(c, idx++);
-        // the last frame whose slot ends within pb of the piece's start
-        const uint32_t cap = n - first < fmax ? n : first + fmax;
-        uint32_t e = (uint32_t)(std::upper_bound(pre + first + 1, pre + cap + 1, pre[first] + pb) - pre) - 1;
-        if (e == first) e = first + 1;  // one frame larger than a piece: alone (it fits the arena)
-        const uint32_t k = e - first;
-        const uint64_t off = pre[e] - pre[first];
-        i = e;
-        {
+    return run_pieces(
+        c, n,
+        [&](Slot&, uint32_t first, uint32_t idx) {
+            // the last frame whose slot ends within the piece's bytes of its
+            // start; one frame larger than a piece goes alone, up to the arena
+            const uint32_t cap = n - first < fmax ? n : first + fmax;
+            uint32_t e =
+                (uint32_t)(std::upper_bound(pre + first + 1, pre + cap + 1, pre[first] + piece_bytes(c, idx)) - pre) - 1;
+            if (e == first && pre[first + 1] - pre[first] <= c->arena) e = first + 1;
+            Cut p;
+            p.k = e - first;
+            p.bytes = pre[e] - pre[first];
+            return p;
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
             const auto t = std::chrono::steady_clock::now();
+            lvlip_frame_desc* hd = (lvlip_frame_desc*)s.h_desc;
             uint8_t* dst = s.h_bytes;
             const lvlip_frame* src = fr + first;
             const uint64_t* pf = pre + first;
             const uint32_t* lf = len ? len + first : nullptr;
-            parallel_ranges(c, k, 256, [=](uint64_t lo, uint64_t hi) {
+            parallel_ranges(c, p.k, 256, [=](uint64_t lo, uint64_t hi) {
                 for (uint64_t q = lo; q < hi; ++q) {
                     // scattered frames: what the copy reads of the frame
                     // kPrefetch frames ahead (scattered 1616-B slots: +25-40 %
@@ -250,14 +148,12 @@ int frames_gather(lvlip_csum_ctx* c, const lvlip_frame* fr, uint32_t n, int mode
                 }
                 _mm_sfence();  // the nontemporal stores land before the copy engine reads
             });
-            if (g_trace.on) g_trace.gather += Trace::ms(t);
-        }
-        fs.first[cur] = first;
-        fs.count[cur] = k;
-        rc = launch_frame_piece(c, s, mode, off ? off : 16, k, out + (size_t)first * ob);
-        cur ^= 1;
-    }
-    return fs.finish(rc, cur);
+            if (c->trace.on) c->trace.gather += Trace::ms(t);
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
+            return launch_frames(c, s, mode, p.bytes ? p.bytes : 16, p.k, out + (size_t)first * ob);
+        },
+        cb);
 }
 
 // Frame descriptors {head - base, len} of k frames, on the pool threads.
@@ -273,80 +169,69 @@ void write_descs(lvlip_csum_ctx* c, lvlip_frame_desc* hd, const lvlip_frame* f, 
 
 // Frames inside one LVLIP_REG_ZEROCOPY region: descriptors only, offsets from
 // the region's first byte rounded down to 16; the kernel reads in place.
+template <class Done>
 int frames_zerocopy(lvlip_csum_ctx* c, const Region& r, const lvlip_frame* fr, uint32_t n, int mode,
-                    uint8_t* out, PieceDone* cb) {
+                    uint8_t* out, Done& cb) {
     const uint8_t* h0 = (const uint8_t*)((uintptr_t)r.host & ~(uintptr_t)15);
     const uint8_t* d0 = r.dev - (r.host - h0);
     const uint32_t fmax = frames_per_piece(c, mode), ob = out_bytes(mode);
-    FrameSlots fs{c, cb};
-    int cur = 0;
-    uint32_t i = 0, idx = 0;
-    int rc = LVLIP_OK;
-    while (i < n && rc == LVLIP_OK) {
-        Slot& s = c->slot[cur];
-        if ((rc = fs.drain_slot(cur)) != LVLIP_OK) break;
-        if (cb && cb->stop()) break;
-        lvlip_frame_desc* hd = (lvlip_frame_desc*)s.h_desc;
-        const uint32_t first = i;
-        const uint64_t pb = piece_bytes(c, idx++);
-        uint64_t bytes = 0;
-        uint32_t k = 0;
-        while (i < n && k < fmax && (k == 0 || bytes + fr[i].len <= pb)) {
-            bytes += fr[i].len;
-            ++k;
-            ++i;
-        }
-        write_descs(c, hd, fr + first, k, (uintptr_t)h0);
-        fs.first[cur] = first;
-        fs.count[cur] = k;
-        rc = launch_frame_piece(c, s, mode, bytes ? bytes : 16, k, out + (size_t)first * ob, nullptr, d0);
-        cur ^= 1;
-    }
-    return fs.finish(rc, cur);
+    return run_pieces(
+        c, n,
+        [&](Slot&, uint32_t first, uint32_t idx) {
+            const uint64_t pb = piece_bytes(c, idx);
+            Cut p;  // nothing is moved: any frame may start a piece
+            for (uint32_t i = first; i < n && p.k < fmax && (p.k == 0 || p.bytes + fr[i].len <= pb); ++i, ++p.k)
+                p.bytes += fr[i].len;
+            return p;
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
+            write_descs(c, (lvlip_frame_desc*)s.h_desc, fr + first, p.k, (uintptr_t)h0);
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
+            return launch_frames(c, s, mode, p.bytes ? p.bytes : 16, p.k, out + (size_t)first * ob, nullptr, d0);
+        },
+        cb);
 }
 
 // Frames inside one LVLIP_REG_DMA region: a piece is a run of frames whose
-// byte span [lo, hi) fits the piece size; the copy engine reads the span from
-// the region.  lo is rounded down to 16 from the region's first byte, not from
-// address 0, so the span never starts before the registered bytes (the copy
-// engine reads them as pinned memory; the kernels take any alignment).
+// byte span [lo, hi) fits the piece size (a single larger one alone, up to the
+// arena); the copy engine reads the span from the region.  lo is rounded down
+// to 16 from the region's first byte, not from address 0, so the span never
+// starts before the registered bytes (the copy engine reads them as pinned
+// memory; the kernels take any alignment).
+// (Pieces grown to the whole arena, as the flat host call's DMA pieces, lost
+// here: TX's last piece's field stores no longer overlap a copy)
+template <class Done>
 int frames_dma(lvlip_csum_ctx* c, const Region& r, const lvlip_frame* fr, uint32_t n, int mode, uint8_t* out,
-               PieceDone* cb) {
+               Done& cb) {
     const uintptr_t r0 = (uintptr_t)r.host;
     const uint32_t fmax = frames_per_piece(c, mode), ob = out_bytes(mode);
-    FrameSlots fs{c, cb};
-    int cur = 0;
-    uint32_t i = 0, idx = 0;
-    int rc = LVLIP_OK;
-    while (i < n && rc == LVLIP_OK) {
-        Slot& s = c->slot[cur];
-        if ((rc = fs.drain_slot(cur)) != LVLIP_OK) break;
-        if (cb && cb->stop()) break;
-        const uint32_t first = i;
-        uintptr_t lo = ~(uintptr_t)0, hi = 0;
-        uint32_t k = 0;
-        // (pieces grown to the whole arena, as the flat host call's DMA pieces,
-        // lost here: TX's last piece's field stores no longer overlap a copy;
-        // DESIGN.md §9)
-        const uint64_t pb = piece_bytes(c, idx++);
-        while (i < n && k < fmax) {
-            const uintptr_t a = (uintptr_t)fr[i].head, e = a + fr[i].len;
-            const uintptr_t a16 = r0 + ((a - r0) & ~(uintptr_t)15);
-            const uintptr_t nlo = a16 < lo ? a16 : lo;
-            const uintptr_t nhi = e > hi ? e : hi;
-            if (align16(nhi - nlo) > (k ? pb : c->arena)) break;  // k = 0: fits (checked)
-            lo = nlo;
-            hi = nhi;
-            ++k;
-            ++i;
-        }
-        write_descs(c, (lvlip_frame_desc*)s.h_desc, fr + first, k, lo);
-        fs.first[cur] = first;
-        fs.count[cur] = k;
-        rc = launch_frame_piece(c, s, mode, hi - lo, k, out + (size_t)first * ob, (const uint8_t*)lo);
-        cur ^= 1;
-    }
-    return fs.finish(rc, cur);
+    return run_pieces(
+        c, n,
+        [&](Slot&, uint32_t first, uint32_t idx) {
+            const uint64_t pb = piece_bytes(c, idx);
+            uintptr_t lo = ~(uintptr_t)0, hi = 0;
+            Cut p;
+            for (uint32_t i = first; i < n && p.k < fmax; ++i, ++p.k) {
+                const uintptr_t a = (uintptr_t)fr[i].head, e = a + fr[i].len;
+                const uintptr_t a16 = r0 + ((a - r0) & ~(uintptr_t)15);
+                const uintptr_t nlo = a16 < lo ? a16 : lo;
+                const uintptr_t nhi = e > hi ? e : hi;
+                if (align16(nhi - nlo) > (p.k ? pb : c->arena)) break;
+                lo = nlo;
+                hi = nhi;
+            }
+            p.lo = lo;
+            p.bytes = hi - lo;
+            return p;
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
+            write_descs(c, (lvlip_frame_desc*)s.h_desc, fr + first, p.k, (uintptr_t)p.lo);
+        },
+        [&](Slot& s, uint32_t first, const Cut& p) {
+            return launch_frames(c, s, mode, p.bytes, p.k, out + (size_t)first * ob, (const uint8_t*)(uintptr_t)p.lo);
+        },
+        cb);
 }
 
 // The region holding every frame (nullptr if there is none), whether the
@@ -364,42 +249,29 @@ RegionScan scan_region(lvlip_csum_ctx* c, const lvlip_frame* fr, uint32_t n) {
     if (c->regions.empty() || !fr[0].head) return out;
     const Region* r = find_region(c, fr[0].head, fr[0].len);
     if (!r) return out;
-    constexpr uint32_t kParts = 256;
-    SpanScan part[kParts];
-    bool in[kParts], fits[kParts];
-    // parts of at least 2048 frames (a small call scans on the calling thread)
-    const uint32_t np = n / 2048u < 1u ? 1u : (n / 2048u > kParts ? kParts : n / 2048u);
     const uint8_t *r0 = r->host, *r1 = r->host + r->bytes;
     const uint64_t arena = c->arena;
-    parallel_ranges(c, np, 1, [&](uint64_t plo, uint64_t phi) {
-        for (uint64_t j = plo; j < phi; ++j) {
-            SpanScan p;
-            bool pin = true, pfits = true;
-            const uint32_t a = (uint32_t)((uint64_t)n * j / np), b = (uint32_t)((uint64_t)n * (j + 1) / np);
-            for (uint32_t i = a; i < b; ++i) {
-                const uint8_t* h = (const uint8_t*)fr[i].head;
-                pin = pin && h && h >= r0 && h + fr[i].len <= r1;
-                span_add(p, (uint64_t)(uintptr_t)h, fr[i].len);
-                pfits = pfits && align16((uint64_t)fr[i].len + 15u) <= arena;
-            }
-            part[j] = p;
-            in[j] = pin;
-            fits[j] = pfits;
-        }
-    });
-    for (uint32_t j = 0; j < np; ++j) {
-        if (!in[j]) return RegionScan{};
-        out.fits = out.fits && fits[j];
-    }
+    std::atomic<bool> unfit{false};
+    SpanScan sc;
+    // parts of at least 2048 frames (a small call scans on the calling thread)
+    if (!span_scan(c, n, 2048, &sc, [&, fr, r0, r1, arena](uint32_t i, SpanScan& p) {
+            const uint8_t* h = (const uint8_t*)fr[i].head;
+            if (!h || h < r0 || h + fr[i].len > r1) return false;
+            span_add(p, (uint64_t)(uintptr_t)h, fr[i].len);
+            if (align16((uint64_t)fr[i].len + 15u) > arena) unfit.store(true, std::memory_order_relaxed);
+            return true;
+        }))
+        return out;
     out.r = r;
-    out.dense = out.fits && span_dense(span_merge(part, np), c->span_ratio);
+    out.fits = !unfit.load(std::memory_order_relaxed);
+    out.dense = out.fits && span_dense(sc, c->span_ratio);
     return out;
 }
 
 // Runs the device step over all n frames; out gets n results (records or
 // verdicts).  Frames are only read.
-int frames_run_(lvlip_csum_ctx* c, const lvlip_frame* fr, uint32_t n, int mode, uint8_t* out,
-                PieceDone* cb) {
+template <class Done>
+int frames_run_(lvlip_csum_ctx* c, const lvlip_frame* fr, uint32_t n, int mode, uint8_t* out, Done& cb) {
     DeviceGuard g(c->device);
     begin_gpu_call(c);
     const RegionScan rs = scan_region(c, fr, n);
@@ -428,7 +300,8 @@ int frames_run_(lvlip_csum_ctx* c, const lvlip_frame* fr, uint32_t n, int mode, 
     constexpr uint32_t kChunk = 4096;
     const uint32_t nch = (n + kChunk - 1) / kChunk;
     const size_t lbytes = mode == M_RX_L4 ? align16(sizeof(uint32_t) * (size_t)n) : 0;
-    uint8_t* sc = (uint8_t*)scratch2(c, lbytes + 8 * ((size_t)n + 1) + 16 * (size_t)nch);
+    uint8_t* sc = (uint8_t*)scratch(c->frame_scratch2, c->frame_scratch2_bytes,
+                                    lbytes + 8 * ((size_t)n + 1) + 16 * (size_t)nch);
     if (!sc) return LVLIP_ENOMEM;
     uint32_t* len = mode == M_RX_L4 ? (uint32_t*)sc : nullptr;
     uint64_t* pre = (uint64_t*)(sc + lbytes);
@@ -468,22 +341,22 @@ int frames_run_(lvlip_csum_ctx* c, const lvlip_frame* fr, uint32_t n, int mode, 
             for (uint32_t i = a; i < b; ++i) pre[i + 1] += tot[2 * j];
         }
     });
-    if (g_trace.on) g_trace.pass1 += Trace::ms(t);
+    if (c->trace.on) c->trace.pass1 += Trace::ms(t);
     if (!fits) return LVLIP_ERANGE;  // a frame larger than the arena
     return frames_gather(c, fr, n, mode, out, len, pre, cb);
 }
 
-int frames_run(lvlip_csum_ctx* c, const lvlip_frame* fr, uint32_t n, int mode, uint8_t* out,
-               PieceDone* cb = nullptr) {
-    g_trace = Trace{};
-    g_trace.on = c->frame_trace != 0;
-    g_trace.t0 = std::chrono::steady_clock::now();
+template <class Done>
+int frames_run(lvlip_csum_ctx* c, const lvlip_frame* fr, uint32_t n, int mode, uint8_t* out, Done& cb) {
+    Trace& tr = c->trace = Trace{};
+    tr.on = c->frame_trace != 0;
+    tr.t0 = std::chrono::steady_clock::now();
     const int rc = frames_run_(c, fr, n, mode, out, cb);
-    if (g_trace.on)
+    if (tr.on)
         fprintf(stderr,
                 "lvlip frames: mode %d n %u pieces %u total %.3f ms pass1 %.3f gather %.3f wait %.3f apply %.3f\n",
-                mode, n, g_trace.pieces, Trace::ms(g_trace.t0), g_trace.pass1, g_trace.gather, g_trace.wait,
-                g_trace.apply);
+                mode, n, tr.pieces, Trace::ms(tr.t0), tr.pass1, tr.gather, tr.wait, tr.apply);
+    tr.on = false;  // the packet calls are not traced
     return rc;
 }
 
@@ -495,15 +368,15 @@ int frames_run(lvlip_csum_ctx* c, const lvlip_frame* fr, uint32_t n, int mode, u
 // every frame it wrote, so a malformed frame leaves the batch untouched as
 // include/lvlip_skb.h promises.
 constexpr uint64_t kApplied = 1ull << 48;  // record bit: this frame was written
-struct TxApply final : PieceDone {
+struct TxApply {
     lvlip_csum_ctx* c;
     lvlip_frame* fr;
     uint64_t* rec;
     uint32_t* undo;
     bool bad = false;
     TxApply(lvlip_csum_ctx* c_, lvlip_frame* f, uint64_t* r, uint32_t* u) : c(c_), fr(f), rec(r), undo(u) {}
-    bool stop() const override { return bad; }
-    void done(uint32_t first, uint32_t k) override {
+    bool stop() const { return bad; }
+    void done(uint32_t first, uint32_t k) {
         if (bad) return;
         for (uint32_t i = first; i < first + k; ++i)
             if (((rec[i] >> 40) & 0xffu) != 1u) {
@@ -536,8 +409,9 @@ struct TxApply final : PieceDone {
     // writing (the pieces were applied in index order; within a frame the L4
     // field was written after the header's)
     void undo_all(uint32_t n) {
-        // last written first: a frame listed twice (in two pieces) gets back
-        // the bytes its first entry saved, the ones from before the call
+        // (a frame listed twice in one call is unsupported, include/lvlip_skb.h:
+        // its entries may be applied on two pool threads at once, and then
+        // neither saved value need be the bytes from before the call)
         for (uint32_t q = n; q-- > 0;) {
             if (!(rec[q] & kApplied)) continue;
             uint8_t* h = fr[q].head;
@@ -582,7 +456,8 @@ int lvlip_rx_verify(lvlip_csum_ctx* ctx, const lvlip_frame* frames, uint32_t n, 
         ctx->stats.cpu_calls++;
         return lvlip_rx_verify_cpu(frames, n, flags, verdict);
     }
-    const int rc = frames_run(ctx, frames, n, mode, verdict);
+    NoDone cb;
+    const int rc = frames_run(ctx, frames, n, mode, verdict, cb);
     trim_scratch(ctx);
     return rc;
 }
@@ -602,7 +477,7 @@ int lvlip_tx_checksum(lvlip_csum_ctx* ctx, lvlip_frame* frames, uint32_t n) {
         return lvlip_tx_checksum_cpu(frames, n);
     }
     // the context's scratch: n records, then n undo words
-    uint64_t* rec = (uint64_t*)scratch(ctx, 12 * (size_t)n);
+    uint64_t* rec = (uint64_t*)scratch(ctx->frame_scratch, ctx->frame_scratch_bytes, 12 * (size_t)n);
     if (!rec) return LVLIP_ENOMEM;
     uint32_t* undo = (uint32_t*)(rec + n);
     // On the pool threads, before the first piece: what needs no frame byte
@@ -620,7 +495,7 @@ int lvlip_tx_checksum(lvlip_csum_ctx* ctx, lvlip_frame* frames, uint32_t n) {
     if (bad.load(std::memory_order_relaxed)) return LVLIP_EINVAL;
     if (any_too_long(ctx, frames, n)) return LVLIP_ERANGE;
     TxApply ap(ctx, frames, rec, undo);
-    int rc = frames_run(ctx, frames, n, M_TX, (uint8_t*)rec, &ap);
+    int rc = frames_run(ctx, frames, n, M_TX, (uint8_t*)rec, ap);
     if (rc == LVLIP_OK && ap.bad) rc = LVLIP_EINVAL;
     if (rc != LVLIP_OK) ap.undo_all(n);  // a malformed frame (or a failure): every frame as it was
     trim_scratch(ctx);

@@ -774,6 +774,29 @@ def test_host_registered_regions_long_packets(flags, name, n):
         ctx.unregister(buf)
 
 
+def test_host_iov_region_span_larger_than_arena():
+    """The iov call over a DMA region, 4 KiB arena: 300 small packets, then one
+    of 4092 B at offset 8 mod 16.  Gathered it fills the arena exactly; as a
+    span (16 B before its first byte's line to the end) it is 4112 B and fits
+    no piece, so the dense path must leave the call to the gather (this
+    divided by zero in launch_piece before the host paths shared one loop)."""
+    rng = np.random.default_rng(11)
+    nbytes = 300 * 64 + 8 + 4092
+    host = np.empty(nbytes + 16, dtype=np.uint8)
+    a = (-host.ctypes.data) % 16
+    buf = host[a:a + nbytes]  # 16-B aligned
+    buf[:] = rng.integers(0, 256, nbytes, dtype=np.uint8)
+    off = [64 * i for i in range(300)] + [300 * 64 + 8]
+    ln = [int(x) for x in rng.integers(1, 61, 300)] + [4092]
+    st = [int(x) for x in rng.integers(0, 2**32, 301)]
+    want = [pyoracle.checksum(buf[o:o + l], l, s) for o, l, s in zip(off, ln, st)]
+    with lvlip.Context(0, arena_bytes=4096, cpu_max=0) as ctx:
+        ctx.register(buf, lvlip.REG_DMA)
+        assert list(ctx.batch_host([buf[o:o + l] for o, l in zip(off, ln)], st)) == want
+        assert list(ctx.batch_host([buf[off[-1]:]], st[-1:])) == want[-1:]
+        ctx.unregister(buf)
+
+
 @pytest.mark.parametrize("gap", [0, 6000])
 def test_host_zerocopy_flat_dense_and_sparse(gap):
     """A flat batch over a LVLIP_REG_ZEROCOPY region: packets that cover their
