@@ -303,6 +303,132 @@ int lvlip_tso_cpu(const void *payload, const lvlip_tso_send *s, uint32_t n, void
 int lvlip_tso_dev(const void *payload, const lvlip_tso_send *s, uint32_t n, uint32_t nseg,
                   void *out, lvlip_frame_desc *fd, void *stream);
 
+/* ---- f1 on the device: receive coalescing ----------------------------------- */
+
+/* The receive half of the data path: tcp_in sets seq, dlen and payload per skb
+ * (src/tcp.c:46-50), tcp_data_queue orders the skbs (src/tcp_data.c:87-128)
+ * and tcp_data_dequeue copies them out one memcpy at a time (:49-85).  For a
+ * receive ring that already lives in HBM these calls do the same per batch, as
+ * a NIC's LRO/GRO does: every frame is parsed as ip_rcv and tcp_in parse it,
+ * matched to a flow, and its payload lands where the byte stream wants it, at
+ * out + out_off + (seq - rcv_nxt).  One record per frame tells the host what
+ * happened; lvlip_lro_advance turns the records into the new rcv_nxt and the
+ * SACK blocks.  The state machine (SYN, RST, URG, the ACK side) stays on the
+ * host: such frames are reported, not interpreted.
+ *
+ * Status of a frame.  2-9 are LVLIP_RX_NOT_IP .. LVLIP_RX_UNKNOWN_PROTO with
+ * the meaning and precedence lvlip_rx_verify_dev gives them for the same flags
+ * (LVLIP_RX_BAD_L4 only with LVLIP_RX_VERIFY_L4).  A frame ip_rcv would keep
+ * gets the lowest of the values below that applies:
+ *   NOT_TCP        ICMP
+ *   BAD_TCP_HDR    hl < 5 or hl*4 > ip.len - ihl*4; also, without
+ *                  LVLIP_RX_VERIFY_L4 (which calls them LVLIP_RX_SHORT), an
+ *                  ip.len below ihl*4 or beyond the frame: the segment the
+ *                  header describes is not in the frame
+ *   NO_FLOW        no planned flow has the frame's addresses and ports
+ *   CONTROL        SYN, RST or URG set: left to the state machine
+ *   NO_DATA        dlen == 0 (a pure ACK, a bare FIN); rel and ack_seq are valid
+ *   OUT_OF_WINDOW  rel + dlen > rcv_wnd in 64-bit arithmetic
+ *   PLACED         the dlen payload bytes are at out + out_off + rel.  FIN with
+ *                  data is placed; the host sees FIN in tcp_flags.
+ * IPv4 and TCP options are accepted and skipped.
+ *
+ * The bytes of `out`.  After the call the dlen bytes at out + out_off + rel
+ * hold the payload of every PLACED frame; where two PLACED frames of a flow
+ * overlap with different bytes the result is either frame's byte (TCP requires
+ * them equal).  Every other byte of `out` is untouched.  With
+ * LVLIP_RX_VERIFY_L4 no byte of a frame is stored before that frame's verdict
+ * is known: a BAD_L4 frame never damages a good one it overlaps.
+ *
+ * Departures from the reference:
+ *   - the window test is mod 2^32 (rel = seq - rcv_nxt); tcp_verify_segment
+ *     (src/tcp_input.c:106-107) compares plain u32 values and breaks when
+ *     rcv_nxt + rcv_wnd wraps;
+ *   - a segment must END inside the window (the reference checks its start
+ *     only; the out buffer needs the bound);
+ *   - partially overlapping segments are united (src/tcp_data.c:16 is a TODO).
+ * For segments that share boundaries, in any arrival order and with
+ * duplicates, out[out_off .. out_off + delivered) is what tcp_data_dequeue
+ * returns and rcv_nxt + delivered what tcp_data_queue leaves in rcv_nxt. */
+#define LVLIP_LRO_PLACED        1
+#define LVLIP_LRO_NOT_TCP       16
+#define LVLIP_LRO_BAD_TCP_HDR   17
+#define LVLIP_LRO_NO_FLOW       18
+#define LVLIP_LRO_CONTROL       19
+#define LVLIP_LRO_NO_DATA       20
+#define LVLIP_LRO_OUT_OF_WINDOW 21
+#define LVLIP_LRO_MAX_FLOWS     65536u
+#define LVLIP_LRO_MAX_WND       0x40000000u
+
+typedef struct lvlip_lro_flow {      /* one connection's receive side; sizeof == 48 */
+    uint32_t saddr, daddr;           /* the words of the frame's IPv4 header (network order) */
+    uint16_t sport, dport;           /* as in the TCP header (network order) */
+    uint32_t rcv_nxt;                /* host order: the first stream byte wanted */
+    uint32_t rcv_wnd;                /* bytes of window = bytes of `out` this flow owns; 1 .. 2^30 */
+    uint32_t reserved;               /* 0 */
+    uint64_t out_off;                /* where stream byte rcv_nxt lands, from the out base; any alignment */
+    uint64_t user;                   /* the caller's cookie; the plan reorders flows */
+    uint8_t  pad[8];                 /* 0 */
+} lvlip_lro_flow;
+
+typedef struct lvlip_lro_rec {       /* one per frame; sizeof == 16, one vector store */
+    uint32_t flow;                   /* index into the planned flows, 0xFFFFFFFF if none */
+    uint32_t rel;                    /* (seq - rcv_nxt) mod 2^32; the raw seq for NO_FLOW */
+    uint16_t dlen;                   /* ip.len - ihl*4 - hl*4, src/tcp.c:47 */
+    uint8_t  status;
+    uint8_t  tcp_flags;              /* byte 13 of the TCP header */
+    uint32_t ack_seq;                /* host order */
+} lvlip_lro_rec;                     /* status below NO_FLOW: flow 0xFFFFFFFF, the rest 0 */
+
+typedef struct lvlip_lro_sack {
+    uint32_t left, right;            /* host-order seq numbers, [left, right) */
+} lvlip_lro_sack;
+
+typedef struct lvlip_lro_result {    /* one per planned flow; sizeof == 48 */
+    uint32_t delivered;              /* contiguous bytes from rel 0: what tcp_data_queue and
+                                        tcp_consume_ofo_queue add to rcv_nxt */
+    uint32_t placed;                 /* PLACED frames of the flow */
+    uint32_t nsack;                  /* islands reported below, 0 .. 4 */
+    uint32_t reserved;               /* 0 */
+    lvlip_lro_sack sack[4];          /* the first islands beyond the prefix in ascending rel, as
+                                        tcp_calculate_sacks walks the ofo queue (src/tcp.c:470-481) */
+} lvlip_lro_result;
+
+/* Host only: validates the flows and sorts them in place by their 12 key
+ * bytes (saddr, daddr, sport, dport) in memcmp order, which is what the
+ * lookup searches.  Returns n, or 0xFFFFFFFF for a duplicate key, rcv_wnd 0 or
+ * above 2^30, nonzero reserved or pad, two flows whose [out_off, out_off +
+ * rcv_wnd) overlap, n above LVLIP_LRO_MAX_FLOWS, or no memory for the overlap
+ * check.  *out_bytes (may be NULL) gets the largest out_off + rcv_wnd: the
+ * bytes `out` must hold. */
+uint32_t lvlip_lro_plan(lvlip_lro_flow *f, uint32_t n, uint64_t *out_bytes);
+
+/* The batch on the calling thread with the library's CPU checksum.  fd[i]
+ * describes frame i inside base, f as lvlip_lro_plan left it; flags 0 or
+ * LVLIP_RX_VERIFY_L4.  Returns 0, or LVLIP_EINVAL (NULL base, fd, out or rec
+ * with n > 0, NULL f with nflows > 0, n above LVLIP_MAX_BATCH, nflows above
+ * LVLIP_LRO_MAX_FLOWS, other flag bits, flows not in plan order) with nothing
+ * written.  nflows == 0 is legal: every TCP frame gets NO_FLOW.  Reentrant. */
+int lvlip_lro_cpu(const void *base, const lvlip_frame_desc *fd, uint32_t n, const lvlip_lro_flow *f,
+                  uint32_t nflows, uint32_t flags, void *out, lvlip_lro_rec *rec);
+
+/* The same records and bytes in one launch on the caller's stream
+ * (asynchronous; no allocation, copy or synchronisation).  All pointers are
+ * device pointers; base as for lvlip_rx_verify_dev (16-B aligned, readable up
+ * to the last frame's end rounded up to 16 B), fd and rec 16-B aligned, f 8-B
+ * aligned, out any alignment.  n == 0 is a no-op; the refusals of
+ * lvlip_lro_cpu are LVLIP_EINVAL before any HIP call, except the flows' order,
+ * which the device does not check: the caller planned them. */
+int lvlip_lro_dev(const void *base, const lvlip_frame_desc *fd, uint32_t n, const lvlip_lro_flow *f,
+                  uint32_t nflows, uint32_t flags, void *out, lvlip_lro_rec *rec, void *stream);
+
+/* Host only: per flow, the union of the PLACED records' [rel, rel + dlen)
+ * (records of other statuses are ignored) -> res[k] for flow k.  Returns 0,
+ * LVLIP_EINVAL (NULL f or res with nflows > 0, NULL rec with n > 0) or
+ * LVLIP_ENOMEM if its scratch allocation fails. */
+int lvlip_lro_advance(const lvlip_lro_flow *f, uint32_t nflows, const lvlip_lro_rec *rec, uint32_t n,
+                      lvlip_lro_result *res);
+
 /* RFC 1071 pseudo-header seed with the carries folded back (for RX verify of
  * checksums produced by RFC-correct peers). */
 uint32_t lvlip_pseudo_sum_rfc(uint32_t saddr, uint32_t daddr, uint8_t proto,

@@ -248,6 +248,15 @@ SIGNATURES = {
                                      ctypes.c_void_p]),
     "lvlip_tso_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # f1 on the device: receive coalescing (rcv_cpu.c, rcv_kernels.hip)
+    "lvlip_lro_plan": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),
+    "lvlip_lro_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "lvlip_lro_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p]),
+    "lvlip_lro_advance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                         ctypes.c_void_p]),
     "lvlip_auto_kernel": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (ctypes.c_char_p, []),
@@ -615,6 +624,100 @@ def tso_dev(payload_t, sends_t, nseg: int, out_t, fd_t=None, stream=None):
         raise ValueError("fd_t: 16 bytes per segment")
     _check(_lib.lvlip_tso_dev(payload_t.data_ptr(), sends_t.data_ptr(), n, nseg, out_t.data_ptr(),
                               fd_t.data_ptr() if fd_t is not None else None, s.cuda_stream), "lvlip_tso_dev")
+
+
+# ------------------------------------- f1 on the device: receive coalescing --
+
+# struct lvlip_lro_flow / lvlip_lro_rec / lvlip_lro_result (include/lvlip_skb.h)
+LRO_FLOW_DTYPE = np.dtype([("saddr", "<u4"), ("daddr", "<u4"), ("sport", "<u2"), ("dport", "<u2"),
+                           ("rcv_nxt", "<u4"), ("rcv_wnd", "<u4"), ("reserved", "<u4"), ("out_off", "<u8"),
+                           ("user", "<u8"), ("pad", "u1", (8,))])
+LRO_REC_DTYPE = np.dtype([("flow", "<u4"), ("rel", "<u4"), ("dlen", "<u2"), ("status", "u1"),
+                          ("tcp_flags", "u1"), ("ack_seq", "<u4")])
+LRO_RESULT_DTYPE = np.dtype([("delivered", "<u4"), ("placed", "<u4"), ("nsack", "<u4"), ("reserved", "<u4"),
+                             ("sack", "<u4", (4, 2))])
+assert LRO_FLOW_DTYPE.itemsize == 48 and LRO_REC_DTYPE.itemsize == 16 and LRO_RESULT_DTYPE.itemsize == 48
+LRO_PLACED, LRO_NOT_TCP, LRO_BAD_TCP_HDR, LRO_NO_FLOW = 1, 16, 17, 18
+LRO_CONTROL, LRO_NO_DATA, LRO_OUT_OF_WINDOW = 19, 20, 21
+LRO_MAX_FLOWS = 65536
+
+
+def lro_flow(saddr: bytes, daddr: bytes, sport: int, dport: int, rcv_nxt: int, rcv_wnd: int, out_off: int = 0,
+             user: int = 0) -> np.ndarray:
+    """One LRO_FLOW_DTYPE record: addresses as the 4 bytes of the IPv4 header,
+    ports as host integers (stored in network order)."""
+    r = np.zeros(1, dtype=LRO_FLOW_DTYPE)
+    r["saddr"] = int.from_bytes(bytes(saddr), "little")
+    r["daddr"] = int.from_bytes(bytes(daddr), "little")
+    r["sport"] = ((sport & 0xFF) << 8) | (sport >> 8)
+    r["dport"] = ((dport & 0xFF) << 8) | (dport >> 8)
+    r["rcv_nxt"], r["rcv_wnd"], r["out_off"], r["user"] = rcv_nxt, rcv_wnd, out_off, user
+    return r
+
+
+def lro_plan(flows: np.ndarray):
+    """lvlip_lro_plan: validates the flows and sorts them in place by key.
+    Returns out_bytes; ValueError for a refused plan."""
+    if flows.dtype != LRO_FLOW_DTYPE or not flows.flags.c_contiguous or not flows.flags.writeable:
+        raise TypeError("flows: a writeable contiguous LRO_FLOW_DTYPE array")
+    out_bytes = ctypes.c_uint64(0)
+    n = int(_lib.lvlip_lro_plan(flows.ctypes.data if flows.size else None, flows.size, ctypes.byref(out_bytes)))
+    if n == PLAN_MALFORMED:
+        raise ValueError("refused flows (duplicate key, window, reserved bytes, overlapping ranges, too many)")
+    return int(out_bytes.value)
+
+
+def lro_cpu(base, fdescs: np.ndarray, flows: np.ndarray, flags: int = 0, out: Optional[np.ndarray] = None):
+    """lvlip_lro_cpu over frames in `base` (uint8) described by FRAME_DESC_DTYPE
+    records, flows as lro_plan left them.  Returns (out, rec): the stream
+    buffer (a new zeroed one of the flows' extent unless `out` is given) and
+    the LRO_REC_DTYPE records."""
+    buf = _as_u8(base)
+    fd = np.ascontiguousarray(fdescs, dtype=FRAME_DESC_DTYPE)
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    if any(int(d["offset"]) + int(d["len"]) > buf.size for d in fd):
+        raise ValueError("a frame lies past the buffer")
+    need = max((int(f["out_off"]) + int(f["rcv_wnd"]) for f in flows), default=0)
+    if out is None:
+        out = np.zeros(need, dtype=np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < need:
+        raise ValueError("out: a contiguous uint8 array of at least the plan's out_bytes")
+    rec = np.zeros(fd.size, dtype=LRO_REC_DTYPE)
+    _check(_lib.lvlip_lro_cpu(buf.ctypes.data, fd.ctypes.data, fd.size, flows.ctypes.data if flows.size else None,
+                              flows.size, flags, out.ctypes.data, rec.ctypes.data), "lvlip_lro_cpu")
+    return out, rec
+
+
+def lro_dev(base_t, fd_t, flows_t, flags: int, out_t, rec_t=None, stream=None):
+    """lvlip_lro_dev on CUDA uint8 tensors: base_t the frames, fd_t 16 bytes per
+    frame (FRAME_DESC_DTYPE), flows_t the planned flows' bytes (48 each, may
+    be empty), out_t the stream buffer.  Returns rec_t (16 bytes per frame, a
+    new tensor unless given).  One launch on `stream` (default: current),
+    asynchronous."""
+    import torch
+
+    n = fd_t.numel() * fd_t.element_size() // 16
+    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize if flows_t is not None else 0
+    if rec_t is None:
+        rec_t = torch.empty(16 * max(n, 1), dtype=torch.uint8, device=out_t.device)
+    elif rec_t.numel() * rec_t.element_size() < 16 * n:
+        raise ValueError("rec_t: 16 bytes per frame")
+    s = stream or torch.cuda.current_stream(out_t.device)
+    _check(_lib.lvlip_lro_dev(base_t.data_ptr(), fd_t.data_ptr(), n, flows_t.data_ptr() if nflows else None, nflows,
+                              flags, out_t.data_ptr(), rec_t.data_ptr(), s.cuda_stream), "lvlip_lro_dev")
+    return rec_t
+
+
+def lro_advance(flows: np.ndarray, rec: np.ndarray) -> np.ndarray:
+    """lvlip_lro_advance: LRO_RESULT_DTYPE per planned flow (delivered, placed,
+    nsack, sack[4] = (left, right))."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    rec = np.ascontiguousarray(rec, dtype=LRO_REC_DTYPE)
+    res = np.zeros(flows.size, dtype=LRO_RESULT_DTYPE)
+    _check(_lib.lvlip_lro_advance(flows.ctypes.data if flows.size else None, flows.size,
+                                  rec.ctypes.data if rec.size else None, rec.size,
+                                  res.ctypes.data if res.size else None), "lvlip_lro_advance")
+    return res
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
