@@ -257,6 +257,9 @@ SIGNATURES = {
                                      ctypes.c_void_p]),
     "lvlip_lro_advance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                          ctypes.c_void_p]),
+    "lvlip_lro_advance_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
+    "lvlip_lro_advance_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "lvlip_auto_kernel": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (ctypes.c_char_p, []),
@@ -718,6 +721,41 @@ def lro_advance(flows: np.ndarray, rec: np.ndarray) -> np.ndarray:
                                   rec.ctypes.data if rec.size else None, rec.size,
                                   res.ctypes.data if res.size else None), "lvlip_lro_advance")
     return res
+
+
+def lro_advance_workspace_bytes(n: int, nflows: int) -> int:
+    """lvlip_lro_advance_workspace_bytes: the device workspace lro_advance_dev
+    needs for n records (0 for n == 0, and without a device)."""
+    return int(_lib.lvlip_lro_advance_workspace_bytes(n, nflows))
+
+
+def lro_advance_dev(flows_t, rec_t, res_t=None, workspace_t=None, stream=None):
+    """lvlip_lro_advance_dev on CUDA uint8 tensors: flows_t the planned flows'
+    bytes (48 each), rec_t 16 bytes per record (what lro_dev returned).
+    Returns res_t, 48 bytes per flow (a new tensor unless given):
+    res_t.cpu().numpy().view(LRO_RESULT_DTYPE) is lro_advance's array.
+    workspace_t (a new tensor unless given) holds at least
+    lro_advance_workspace_bytes(n, nflows) bytes at a 256-B aligned address.
+    Asynchronous on `stream` (default: current)."""
+    import torch
+
+    n = rec_t.numel() * rec_t.element_size() // 16 if rec_t is not None else 0
+    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize if flows_t is not None else 0
+    device = flows_t.device if flows_t is not None else rec_t.device
+    if res_t is None:
+        res_t = torch.empty(LRO_RESULT_DTYPE.itemsize * max(nflows, 1), dtype=torch.uint8, device=device)
+    elif res_t.numel() * res_t.element_size() < LRO_RESULT_DTYPE.itemsize * nflows:
+        raise ValueError("res_t: 48 bytes per flow")
+    need = lro_advance_workspace_bytes(n, nflows) if n and nflows else 0
+    if workspace_t is None and need:
+        workspace_t = torch.empty(need, dtype=torch.uint8, device=device)
+    s = stream or torch.cuda.current_stream(device)
+    _check(_lib.lvlip_lro_advance_dev(flows_t.data_ptr() if nflows else None, nflows,
+                                      rec_t.data_ptr() if n else None, n, res_t.data_ptr(),
+                                      workspace_t.data_ptr() if workspace_t is not None else None,
+                                      workspace_t.numel() * workspace_t.element_size() if workspace_t is not None
+                                      else 0, s.cuda_stream), "lvlip_lro_advance_dev")
+    return res_t[:LRO_RESULT_DTYPE.itemsize * nflows]
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
