@@ -462,6 +462,89 @@ size_t lvlip_lro_advance_workspace_bytes(uint32_t n, uint32_t nflows);
 int lvlip_lro_advance_dev(const lvlip_lro_flow *f, uint32_t nflows, const lvlip_lro_rec *rec, uint32_t n,
                           lvlip_lro_result *res, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- f1 on the device: the acknowledgement --------------------------------- */
+
+/* What follows the advance step in the reference's receive path is
+ * tcp_send_ack (src/tcp_output.c:247-267) -> tcp_transmit_skb (:93-129) ->
+ * ip_output (src/ip_output.c:14-56): one pure ACK per connection, with the
+ * SACK option tcp_write_options writes (src/tcp_output.c:65-91), the only TCP
+ * option the reference writes outside a SYN.  These calls build that frame
+ * per planned flow from a 54-byte header template and the flow's
+ * lvlip_lro_result, so that lvlip_lro_dev -> lvlip_lro_advance_dev ->
+ * lvlip_ack_dev turns frames in HBM into stream bytes and ACK frames in HBM on
+ * one stream, with no host step.
+ *
+ * The frame of flow k.  b = min(res[k].nsack, t[k].max_sack, 4) (the clamp
+ * holds for a res no library call wrote), optlen = b ? 4 + 8 b : 0; the frame
+ * is the 54 + optlen bytes at out + t[k].out_off:
+ *   Ethernet  the template's 14 bytes
+ *   IPv4      the template, total length htons(40 + optlen), header checksum
+ *             checksum(ih, 20, 0) with the field zeroed first, stored raw
+ *             (src/ip_output.c:42,53)
+ *   TCP       the template, ack_seq = htonl(f[k].rcv_nxt + res[k].delivered)
+ *             mod 2^32 (src/tcp_output.c:107); the data offset nibble
+ *             5 + optlen/4 (:261), the low nibble of that byte as the template
+ *             has it; when b > 0 the option bytes 01 01 05 (2 + 8 b), then the
+ *             blocks sack[b-1], ..., sack[0], each htonl(left), htonl(right):
+ *             DESCENDING, as tcp_write_options walks i = sacklen-1 .. 0
+ *             (src/tcp_output.c:78-86); csum = checksum(tcp, 20 + optlen,
+ *             saddr + daddr + htons(6) + htons(20 + optlen)) stored raw, the
+ *             seed a u32 that wraps (src/tcp.c:87-98: the carry is lost, as in
+ *             lvlip_pseudo_sum and lvlip_tso_dev)
+ * and, when fd is given, fd[k] = {t[k].out_off, 54 + optlen, 0}, which the
+ * other _dev calls take as it is.  Without LVLIP_ACK_ALL a flow with
+ * res[k].placed == 0 gets no ACK: no byte of `out` is written for it and
+ * fd[k] = {t[k].out_off, 0, 0}.  Nothing outside the frames is written (the
+ * rest of a 90-byte slot keeps its bytes); t, f and res are only read.
+ *
+ * Departure from the reference: tcp_write_options and tcp_options_len treat a
+ * block whose left edge is sequence number 0 as absent
+ * (src/tcp_output.c:69,234).  Here every one of the b blocks is written. */
+#define LVLIP_ACK_MAX_FRAME 90u       /* 14 + 20 + 20 + 4 + 4*8 */
+#define LVLIP_ACK_ALL       0x1u      /* flags: an ACK for every flow; 0 = only flows with res.placed > 0 */
+
+typedef struct lvlip_ack_tmpl {       /* one per planned flow, index k = flow k in plan order; sizeof == 64 */
+    uint64_t out_off;                 /* where the frame goes, from the out base; any alignment */
+    uint8_t  hdr[54];                 /* Ethernet, IPv4 (ihl 5), TCP (hl 5), network order: what the stack's
+                                         own next pure ACK of this connection would carry (seq = snd_nxt, win,
+                                         flags, id, addresses, ports); IP length, ack_seq, data offset and both
+                                         checksum fields are ignored */
+    uint8_t  max_sack;                /* tsk->sacks_allowed: 0 (SACK not negotiated) .. 4 */
+    uint8_t  reserved;                /* 0 */
+} lvlip_ack_tmpl;
+
+/* Host only: validates the templates against the planned flows.  Returns
+ * nflows, or 0xFFFFFFFF for a template whose ethertype is not 0x0800, whose
+ * version/ihl is not 0x45, whose protocol is not 6 or whose TCP header length
+ * is not 5; max_sack above 4; nonzero reserved; a template that is not the
+ * reverse of its flow (hdr.saddr == f.daddr, hdr.daddr == f.saddr, hdr.sport
+ * == f.dport and hdr.dport == f.sport must all hold: lvlip_lro_plan reorders
+ * flows, and this catches templates left in the old order); two slots
+ * [out_off, out_off + 90) that overlap; nflows above LVLIP_LRO_MAX_FLOWS; or no
+ * memory for the overlap check.  *out_bytes (may be NULL) gets the largest
+ * out_off + 90: the bytes `out` must hold.  Nothing is modified. */
+uint32_t lvlip_ack_plan(const lvlip_ack_tmpl *t, const lvlip_lro_flow *f, uint32_t nflows, uint64_t *out_bytes);
+
+/* The frames on the calling thread, one checksum() per field (the library's
+ * CPU code).  Returns 0, or LVLIP_EINVAL (NULL t, f, res or out with
+ * nflows > 0, flag bits other than LVLIP_ACK_ALL, nflows above
+ * LVLIP_LRO_MAX_FLOWS) with nothing written.  nflows == 0 is a no-op.
+ * Reentrant; fd may be NULL. */
+int lvlip_ack_cpu(const lvlip_ack_tmpl *t, const lvlip_lro_flow *f, const lvlip_lro_result *res,
+                  uint32_t nflows, uint32_t flags, void *out, lvlip_frame_desc *fd);
+
+/* The same frames and fd, bit for bit, in one launch on the caller's stream
+ * (asynchronous; no allocation, copy, workspace, atomics or synchronisation).
+ * All pointers are device pointers: t and f 8-B aligned, res and fd 16-B
+ * aligned, out any alignment; res as lvlip_lro_advance_dev left it on the same
+ * stream, or any other.  The refusals of lvlip_ack_cpu, and a misaligned t,
+ * f, res or fd, are LVLIP_EINVAL before any HIP call; LVLIP_ENODEV without a
+ * device; a failed launch is LVLIP_EHIP (lvlip_last_hip_error).  The device
+ * does not validate the templates again: the caller planned them.  Measured:
+ * DESIGN.md §9d. */
+int lvlip_ack_dev(const lvlip_ack_tmpl *t, const lvlip_lro_flow *f, const lvlip_lro_result *res,
+                  uint32_t nflows, uint32_t flags, void *out, lvlip_frame_desc *fd, void *stream);
+
 /* RFC 1071 pseudo-header seed with the carries folded back (for RX verify of
  * checksums produced by RFC-correct peers). */
 uint32_t lvlip_pseudo_sum_rfc(uint32_t saddr, uint32_t daddr, uint8_t proto,

@@ -260,6 +260,13 @@ SIGNATURES = {
     "lvlip_lro_advance_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
     "lvlip_lro_advance_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # f1 on the device: the acknowledgement (ack_cpu.c, ack_kernels.hip)
+    "lvlip_ack_plan": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                         ctypes.POINTER(ctypes.c_uint64)]),
+    "lvlip_ack_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "lvlip_ack_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "lvlip_auto_kernel": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (ctypes.c_char_p, []),
@@ -756,6 +763,85 @@ def lro_advance_dev(flows_t, rec_t, res_t=None, workspace_t=None, stream=None):
                                       workspace_t.numel() * workspace_t.element_size() if workspace_t is not None
                                       else 0, s.cuda_stream), "lvlip_lro_advance_dev")
     return res_t[:LRO_RESULT_DTYPE.itemsize * nflows]
+
+
+# ------------------------------------- f1 on the device: the acknowledgement --
+
+# struct lvlip_ack_tmpl (include/lvlip_skb.h), 64 B
+ACK_TMPL_DTYPE = np.dtype([("out_off", "<u8"), ("hdr", "u1", (54,)), ("max_sack", "u1"), ("reserved", "u1")])
+assert ACK_TMPL_DTYPE.itemsize == 64
+ACK_MAX_FRAME = 90
+ACK_ALL = 1
+
+
+def ack_tmpl(hdr, out_off: int = 0, max_sack: int = 4) -> np.ndarray:
+    """One ACK_TMPL_DTYPE record from the 54 header bytes of the connection's
+    own pure ACK."""
+    r = np.zeros(1, dtype=ACK_TMPL_DTYPE)
+    r["out_off"], r["max_sack"] = out_off, max_sack
+    r["hdr"][0] = np.frombuffer(bytes(hdr)[:54], dtype=np.uint8)
+    return r
+
+
+def ack_plan(tmpl: np.ndarray, flows: np.ndarray) -> int:
+    """lvlip_ack_plan: validates the templates against the planned flows
+    (template k answers flow k).  Returns out_bytes; ValueError for a refused
+    plan."""
+    if tmpl.dtype != ACK_TMPL_DTYPE or not tmpl.flags.c_contiguous:
+        raise TypeError("tmpl: a contiguous ACK_TMPL_DTYPE array")
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    if tmpl.size != flows.size:
+        raise ValueError("one template per flow")
+    out_bytes = ctypes.c_uint64(0)
+    n = int(_lib.lvlip_ack_plan(tmpl.ctypes.data if tmpl.size else None, flows.ctypes.data if flows.size else None,
+                                flows.size, ctypes.byref(out_bytes)))
+    if n == PLAN_MALFORMED:
+        raise ValueError("refused templates (header, max_sack, reserved, not the flow's reverse, overlapping slots, "
+                         "too many)")
+    return int(out_bytes.value)
+
+
+def ack_cpu(tmpl: np.ndarray, flows: np.ndarray, res: np.ndarray, flags: int = 0,
+            out: Optional[np.ndarray] = None):
+    """lvlip_ack_cpu: plans the templates and builds the ACK frames on the
+    calling thread.  Returns (out, fd): the frame buffer (a new zeroed one of
+    the plan's out_bytes unless `out` is given, which then keeps its bytes
+    outside the frames) and the FRAME_DESC_DTYPE descriptors, one per flow."""
+    out_bytes = ack_plan(tmpl, flows)
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    res = np.ascontiguousarray(res, dtype=LRO_RESULT_DTYPE)
+    if res.size != flows.size:
+        raise ValueError("one result per flow")
+    if out is None:
+        out = np.zeros(out_bytes, dtype=np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < out_bytes:
+        raise ValueError("out: a contiguous uint8 array of at least the plan's out_bytes")
+    fd = np.zeros(flows.size, dtype=FRAME_DESC_DTYPE)
+    _check(_lib.lvlip_ack_cpu(tmpl.ctypes.data if tmpl.size else None, flows.ctypes.data if flows.size else None,
+                              res.ctypes.data if res.size else None, flows.size, flags, out.ctypes.data,
+                              fd.ctypes.data if fd.size else None), "lvlip_ack_cpu")
+    return out, fd
+
+
+def ack_dev(tmpl_t, flows_t, res_t, flags: int, out_t, fd_t=None, stream=None):
+    """lvlip_ack_dev on CUDA uint8 tensors: tmpl_t the planned templates' bytes
+    (64 each), flows_t the planned flows' bytes (48 each), res_t 48 bytes per
+    flow (what lro_advance_dev returned), out_t the frame buffer (at least the
+    plan's out_bytes), fd_t (optional) 16 bytes per flow for the frame
+    descriptors.  One launch on `stream` (default: current), asynchronous."""
+    import torch
+
+    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize
+    if tmpl_t.numel() * tmpl_t.element_size() < ACK_TMPL_DTYPE.itemsize * nflows:
+        raise ValueError("tmpl_t: 64 bytes per flow")
+    if res_t.numel() * res_t.element_size() < LRO_RESULT_DTYPE.itemsize * nflows:
+        raise ValueError("res_t: 48 bytes per flow")
+    if fd_t is not None and fd_t.numel() * fd_t.element_size() < 16 * nflows:
+        raise ValueError("fd_t: 16 bytes per flow")
+    s = stream or torch.cuda.current_stream(out_t.device)
+    _check(_lib.lvlip_ack_dev(tmpl_t.data_ptr(), flows_t.data_ptr(), res_t.data_ptr(), nflows, flags,
+                              out_t.data_ptr(), fd_t.data_ptr() if fd_t is not None else None, s.cuda_stream),
+           "lvlip_ack_dev")
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
