@@ -1,0 +1,186 @@
+/*
+ * snd_cpu.c — the ACK side of a coalesced batch and the retransmit
+ * (include/lvlip_skb.h, "f2 on the device: the ACK side and the retransmit"):
+ * the plan, and both calls on the calling thread.  The device forms
+ * (snd_kernels.hip) leave the same bytes.
+ *
+ * lvlip_snd_cpu is the fifth check of tcp_input_state (src/tcp_input.c:311-356)
+ * with tcp_clean_rto_queue (:66-92) over the records of one lvlip_lro_* call;
+ * lvlip_rtx_cpu is what tcp_retransmission_timeout (src/tcp_output.c:359-381)
+ * and tcp_send_next (:198-225) do to a queued segment: tcp_transmit_skb
+ * (:93-129) writes ack_seq and the window again and sums the whole segment.
+ */
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "lvlip_skb.h"
+
+#define SND_HDR 54u /* Ethernet 14 + IPv4 20 + TCP 20 */
+#define NONE 0xFFFFFFFFu
+#define ACK_FLAG 0x10u
+
+static inline uint32_t le32(const uint8_t *p)
+{
+    uint32_t v;
+    memcpy(&v, p, 4);
+    return v;
+}
+
+static inline uint32_t be32(const uint8_t *p)
+{
+    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+}
+
+static inline void put_be32(uint8_t *p, uint32_t v)
+{
+    p[0] = (uint8_t)(v >> 24);
+    p[1] = (uint8_t)(v >> 16);
+    p[2] = (uint8_t)(v >> 8);
+    p[3] = (uint8_t)v;
+}
+
+static inline uint16_t bswap16(uint16_t x) { return (uint16_t)((x << 8) | (x >> 8)); }
+
+/* ------------------------------------------------------------------ plan -- */
+
+typedef struct {
+    uint32_t seg0, nseg;
+} queue_range;
+
+static int range_cmp(const void *a, const void *b)
+{
+    const uint32_t x = ((const queue_range *)a)->seg0, y = ((const queue_range *)b)->seg0;
+    return x < y ? -1 : x > y;
+}
+
+uint32_t lvlip_snd_plan(lvlip_snd_flow *s, uint32_t nflows, uint32_t *nfd)
+{
+    if (nfd) *nfd = 0;
+    if (nflows == 0) return 0;
+    if (!s || nflows > LVLIP_LRO_MAX_FLOWS) return NONE;
+    uint64_t segs = 0, slots = 0;
+    uint32_t top = 0, queues = 0;
+    for (uint32_t k = 0; k < nflows; k++) {
+        if (s[k].reserved != 0 || s[k].reserved2 != 0) return NONE;
+        if ((uint32_t)(s[k].snd_nxt - s[k].snd_una) > 0x40000000u) return NONE;
+        if ((uint64_t)s[k].seg0 + s[k].nseg > 0xFFFFFFFFull) return NONE;
+        segs += s[k].nseg;
+        slots += s[k].rtx;
+        if (s[k].nseg) {
+            queues++;
+            if (s[k].seg0 + s[k].nseg > top) top = s[k].seg0 + s[k].nseg;
+        }
+    }
+    if (segs > LVLIP_MAX_BATCH || slots > LVLIP_MAX_BATCH) return NONE;
+    /* the queues, sorted by their first entry: each must end before the next begins */
+    if (queues > 1u) {
+        queue_range *r = malloc((size_t)queues * sizeof *r);
+        if (!r) return NONE;
+        uint32_t m = 0;
+        for (uint32_t k = 0; k < nflows; k++)
+            if (s[k].nseg) r[m].seg0 = s[k].seg0, r[m++].nseg = s[k].nseg;
+        qsort(r, m, sizeof *r, range_cmp);
+        int bad = 0;
+        for (uint32_t k = 1; k < m && !bad; k++) bad = r[k].seg0 - r[k - 1u].seg0 < r[k - 1u].nseg;
+        free(r);
+        if (bad) return NONE;
+    }
+    uint32_t slot = 0;
+    for (uint32_t k = 0; k < nflows; k++) {
+        s[k].slot0 = slot;
+        slot += s[k].rtx;
+    }
+    if (nfd) *nfd = top;
+    return slot;
+}
+
+/* -------------------------------------------------------------- ACK side -- */
+
+/* seq + dlen of the frame at p (src/tcp.c:46-50), from its 54 header bytes */
+static inline uint32_t frame_end_seq(const uint8_t *p)
+{
+    const uint32_t iplen = ((uint32_t)p[16] << 8) | p[17];
+    return be32(p + 38) + iplen - 4u * (p[14] & 0x0fu) - 4u * (p[46] >> 4);
+}
+
+int lvlip_snd_cpu(const lvlip_lro_flow *f, const lvlip_snd_flow *s, uint32_t nflows, const lvlip_lro_rec *rec,
+                  uint32_t n, const void *base, const lvlip_frame_desc *fd, lvlip_snd_result *res)
+{
+    if (nflows == 0 || n == 0) return LVLIP_OK;
+    if (!f || !s || !rec || !base || !fd || !res) return LVLIP_EINVAL;
+    if (n > LVLIP_MAX_BATCH || nflows > LVLIP_LRO_MAX_FLOWS) return LVLIP_EINVAL;
+    memset(res, 0, (size_t)nflows * sizeof *res);
+    for (uint32_t i = 0; i < n; i++) {
+        const lvlip_lro_rec *r = &rec[i];
+        const uint32_t k = r->flow;
+        if (k >= nflows) continue;
+        if (r->status != LVLIP_LRO_PLACED && r->status != LVLIP_LRO_NO_DATA && r->status != LVLIP_LRO_OUT_OF_WINDOW)
+            continue;
+        /* fifth check, src/tcp_input.c:312; first check, :106-107, on the segment's start */
+        if (!(r->tcp_flags & ACK_FLAG) || r->rel > f[k].rcv_wnd) continue;
+        const uint32_t d = r->ack_seq - s[k].snd_una, span = s[k].snd_nxt - s[k].snd_una;
+        if (d == 0) {
+            res[k].n_dup++;
+        } else if (d <= span) { /* src/tcp_input.c:330-331: snd_una only ever rises */
+            res[k].n_new++;
+            if (d > res[k].acked) res[k].acked = d;
+        } else if (d >= 0x80000000u) { /* :338 */
+            res[k].n_old++;
+        } else { /* :343 */
+            res[k].n_beyond++;
+        }
+    }
+    for (uint32_t k = 0; k < nflows; k++) {
+        res[k].snd_una = s[k].snd_una + res[k].acked;
+        /* tcp_clean_rto_queue, src/tcp_input.c:72-84: stop at the first frame not fully acknowledged */
+        uint32_t p = 0;
+        for (; p < s[k].nseg; p++) {
+            const lvlip_frame_desc *d = &fd[s[k].seg0 + p];
+            if (d->len < SND_HDR) break;
+            if (frame_end_seq((const uint8_t *)base + d->offset) - s[k].snd_una > res[k].acked) break;
+        }
+        res[k].popped = p;
+        res[k].inflight = s[k].nseg - p;
+    }
+    return LVLIP_OK;
+}
+
+/* ------------------------------------------------------------ retransmit -- */
+
+int lvlip_rtx_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, const lvlip_snd_flow *s,
+                  const lvlip_snd_result *snd, uint32_t nflows, uint32_t nslots, void *base,
+                  const lvlip_frame_desc *fd, lvlip_frame_desc *fd_out)
+{
+    if (nslots == 0) return LVLIP_OK;
+    if (!f || !s || !base || !fd || !fd_out) return LVLIP_EINVAL;
+    if (nflows == 0 || nflows > LVLIP_LRO_MAX_FLOWS || nslots > LVLIP_MAX_BATCH) return LVLIP_EINVAL;
+    if (s[nflows - 1u].slot0 > nslots || nslots - s[nflows - 1u].slot0 != s[nflows - 1u].rtx) return LVLIP_EINVAL;
+    for (uint32_t k = 0; k < nflows; k++) {
+        const uint32_t popped = snd ? snd[k].popped : 0u;
+        const uint32_t ack = f[k].rcv_nxt + (lro ? lro[k].delivered : 0u);
+        for (uint32_t j = 0; j < s[k].rtx; j++) {
+            lvlip_frame_desc *o = &fd_out[s[k].slot0 + j];
+            o->offset = 0, o->len = 0, o->reserved = 0;
+            if (popped >= s[k].nseg || j >= s[k].nseg - popped) continue;
+            const lvlip_frame_desc d = fd[s[k].seg0 + popped + j];
+            if (d.len < SND_HDR) continue;
+            uint8_t *p = (uint8_t *)base + d.offset, *ih = p + 14, *th = p + 34;
+            const uint32_t iplen = ((uint32_t)ih[2] << 8) | ih[3], hl = th[12] >> 4;
+            if (ih[0] != 0x45 || 14u + iplen > d.len || hl < 5u || 20u + 4u * hl > iplen) continue;
+            /* tcp_transmit_skb, src/tcp_output.c:107,109,110 and :122,123 */
+            put_be32(th + 8, ack);
+            th[14] = (uint8_t)(s[k].win >> 8);
+            th[15] = (uint8_t)s[k].win;
+            th[16] = th[17] = 0;
+            /* tcp_v4_checksum, :126; src/tcp.c:92-95: u32 adds, the carry out of bit 31 is lost */
+            const uint16_t l4 = (uint16_t)(iplen - 20u);
+            const uint32_t seed = le32(ih + 12) + le32(ih + 16) + bswap16(6) + bswap16(l4);
+            const uint16_t tc = checksum(th, (int)l4, (int)seed);
+            memcpy(th + 16, &tc, 2);
+            *o = d;
+        }
+    }
+    return LVLIP_OK;
+}

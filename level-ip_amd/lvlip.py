@@ -267,6 +267,19 @@ SIGNATURES = {
                                      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "lvlip_ack_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # f2 on the device: the ACK side and the retransmit (snd_cpu.c, snd_kernels.hip)
+    "lvlip_snd_plan": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "lvlip_snd_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "lvlip_snd_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p]),
+    "lvlip_rtx_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p]),
+    "lvlip_rtx_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p]),
     "lvlip_auto_kernel": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (ctypes.c_char_p, []),
@@ -842,6 +855,142 @@ def ack_dev(tmpl_t, flows_t, res_t, flags: int, out_t, fd_t=None, stream=None):
     _check(_lib.lvlip_ack_dev(tmpl_t.data_ptr(), flows_t.data_ptr(), res_t.data_ptr(), nflows, flags,
                               out_t.data_ptr(), fd_t.data_ptr() if fd_t is not None else None, s.cuda_stream),
            "lvlip_ack_dev")
+
+
+# ------------------------- f2 on the device: the ACK side and the retransmit --
+
+# struct lvlip_snd_flow / lvlip_snd_result (include/lvlip_skb.h), 32 B each
+SND_FLOW_DTYPE = np.dtype([("snd_una", "<u4"), ("snd_nxt", "<u4"), ("seg0", "<u4"), ("nseg", "<u4"),
+                           ("slot0", "<u4"), ("rtx", "<u4"), ("win", "<u2"), ("reserved", "<u2"),
+                           ("reserved2", "<u4")])
+SND_RESULT_DTYPE = np.dtype([("snd_una", "<u4"), ("acked", "<u4"), ("n_new", "<u4"), ("n_dup", "<u4"),
+                             ("n_old", "<u4"), ("n_beyond", "<u4"), ("popped", "<u4"), ("inflight", "<u4")])
+assert SND_FLOW_DTYPE.itemsize == 32 and SND_RESULT_DTYPE.itemsize == 32
+
+
+def snd_plan(snd: np.ndarray):
+    """lvlip_snd_plan: validates the flows' send sides and fills slot0 in
+    place.  Returns (nslots, nfd); ValueError for a refused plan."""
+    if snd.dtype != SND_FLOW_DTYPE or not snd.flags.c_contiguous or not snd.flags.writeable:
+        raise TypeError("snd: a writeable contiguous SND_FLOW_DTYPE array")
+    nfd = ctypes.c_uint32(0)
+    n = int(_lib.lvlip_snd_plan(snd.ctypes.data if snd.size else None, snd.size, ctypes.byref(nfd)))
+    if n == PLAN_MALFORMED:
+        raise ValueError("refused send sides (reserved bytes, snd_nxt - snd_una, overlapping queues, too many)")
+    return n, int(nfd.value)
+
+
+def _ring(base, fdescs, snd):
+    buf = base if isinstance(base, np.ndarray) and base.dtype == np.uint8 and base.flags.c_contiguous else _as_u8(base)
+    fd = np.ascontiguousarray(fdescs, dtype=FRAME_DESC_DTYPE)
+    ends = snd["seg0"].astype(np.uint64) + snd["nseg"]
+    if ((snd["nseg"] > 0) & (ends > fd.size)).any():
+        raise ValueError("a queue lies past fd")
+    if (fd["offset"] + fd["len"].astype(np.uint64) > buf.size).any():
+        raise ValueError("a frame lies past the ring")
+    return buf, fd
+
+
+def snd_cpu(flows: np.ndarray, snd: np.ndarray, rec: np.ndarray, base, fdescs: np.ndarray) -> np.ndarray:
+    """lvlip_snd_cpu: the ACK side of one lro_* call's records.  flows the
+    planned LRO_FLOW_DTYPE array, snd as snd_plan left it, base / fdescs the TX
+    ring that holds the write queues.  Returns SND_RESULT_DTYPE per flow
+    (zeros when there is no record: the call is a no-op then)."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    snd = np.ascontiguousarray(snd, dtype=SND_FLOW_DTYPE)
+    rec = np.ascontiguousarray(rec, dtype=LRO_REC_DTYPE)
+    if snd.size != flows.size:
+        raise ValueError("one send side per flow")
+    buf, fd = _ring(base, fdescs, snd)
+    res = np.zeros(flows.size, dtype=SND_RESULT_DTYPE)
+    keep = np.zeros(16, dtype=np.uint8)  # stands in for an empty ring: the call wants non-NULL pointers
+    _check(_lib.lvlip_snd_cpu(flows.ctypes.data if flows.size else None, snd.ctypes.data if snd.size else None,
+                              flows.size, rec.ctypes.data if rec.size else None, rec.size,
+                              buf.ctypes.data if buf.size else keep.ctypes.data,
+                              fd.ctypes.data if fd.size else keep.ctypes.data,
+                              res.ctypes.data if res.size else None), "lvlip_snd_cpu")
+    return res
+
+
+def snd_dev(flows_t, snd_t, rec_t, base_t, fd_t, res_t=None, stream=None):
+    """lvlip_snd_dev on CUDA uint8 tensors: flows_t the planned flows' bytes
+    (48 each), snd_t the planned send sides' (32 each), rec_t 16 bytes per
+    record (what lro_dev returned), base_t / fd_t the TX ring and its
+    descriptors.  Returns res_t, 32 bytes per flow (a new tensor unless
+    given).  Asynchronous on `stream` (default: current)."""
+    import torch
+
+    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize
+    n = rec_t.numel() * rec_t.element_size() // 16 if rec_t is not None else 0
+    if snd_t.numel() * snd_t.element_size() < SND_FLOW_DTYPE.itemsize * nflows:
+        raise ValueError("snd_t: 32 bytes per flow")
+    if res_t is None:
+        res_t = torch.zeros(SND_RESULT_DTYPE.itemsize * max(nflows, 1), dtype=torch.uint8, device=flows_t.device)
+    elif res_t.numel() * res_t.element_size() < SND_RESULT_DTYPE.itemsize * nflows:
+        raise ValueError("res_t: 32 bytes per flow")
+    s = stream or torch.cuda.current_stream(flows_t.device)
+    _check(_lib.lvlip_snd_dev(flows_t.data_ptr(), snd_t.data_ptr(), nflows, rec_t.data_ptr() if n else None, n,
+                              base_t.data_ptr(), fd_t.data_ptr(), res_t.data_ptr(), s.cuda_stream), "lvlip_snd_dev")
+    return res_t[:SND_RESULT_DTYPE.itemsize * nflows]
+
+
+def rtx_cpu(flows: np.ndarray, lro_res, snd: np.ndarray, snd_res, base: np.ndarray, fdescs: np.ndarray) -> np.ndarray:
+    """lvlip_rtx_cpu: rewrites the live frames at the head of every queue IN
+    PLACE in `base` (a writeable contiguous uint8 array).  lro_res
+    (LRO_RESULT_DTYPE per flow) and snd_res (SND_RESULT_DTYPE per flow) may be
+    None.  Returns fd_out, FRAME_DESC_DTYPE per slot ({0, 0, 0} = no frame)."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    snd = np.ascontiguousarray(snd, dtype=SND_FLOW_DTYPE)
+    if snd.size != flows.size:
+        raise ValueError("one send side per flow")
+    if not isinstance(base, np.ndarray) or base.dtype != np.uint8 or not base.flags.c_contiguous or \
+            not base.flags.writeable:
+        raise TypeError("base: a writeable contiguous uint8 array (the ring is rewritten in place)")
+    _, fd = _ring(base, fdescs, snd)
+    if lro_res is not None:
+        lro_res = np.ascontiguousarray(lro_res, dtype=LRO_RESULT_DTYPE)
+    if snd_res is not None:
+        snd_res = np.ascontiguousarray(snd_res, dtype=SND_RESULT_DTYPE)
+    if any(r is not None and r.size != flows.size for r in (lro_res, snd_res)):
+        raise ValueError("one result per flow")
+    nslots = int(snd["rtx"].astype(np.uint64).sum()) if snd.size else 0
+    fd_out = np.zeros(nslots, dtype=FRAME_DESC_DTYPE)
+    keep = np.zeros(16, dtype=np.uint8)
+    _check(_lib.lvlip_rtx_cpu(flows.ctypes.data if flows.size else None,
+                              lro_res.ctypes.data if lro_res is not None and lro_res.size else None,
+                              snd.ctypes.data if snd.size else None,
+                              snd_res.ctypes.data if snd_res is not None and snd_res.size else None,
+                              flows.size, nslots, base.ctypes.data if base.size else keep.ctypes.data,
+                              fd.ctypes.data if fd.size else keep.ctypes.data,
+                              fd_out.ctypes.data if fd_out.size else None), "lvlip_rtx_cpu")
+    return fd_out
+
+
+def rtx_dev(flows_t, lro_res_t, snd_t, snd_res_t, nslots: int, base_t, fd_t, fd_out_t=None, stream=None):
+    """lvlip_rtx_dev on CUDA uint8 tensors: one launch that rewrites the live
+    frames in base_t in place.  lro_res_t (48 bytes per flow) and snd_res_t (32
+    per flow) may be None; nslots is what snd_plan returned.  Returns
+    fd_out_t, 16 bytes per slot (a new tensor unless given).  Asynchronous on
+    `stream` (default: current)."""
+    import torch
+
+    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize
+    if snd_t.numel() * snd_t.element_size() < SND_FLOW_DTYPE.itemsize * nflows:
+        raise ValueError("snd_t: 32 bytes per flow")
+    if lro_res_t is not None and lro_res_t.numel() * lro_res_t.element_size() < LRO_RESULT_DTYPE.itemsize * nflows:
+        raise ValueError("lro_res_t: 48 bytes per flow")
+    if snd_res_t is not None and snd_res_t.numel() * snd_res_t.element_size() < SND_RESULT_DTYPE.itemsize * nflows:
+        raise ValueError("snd_res_t: 32 bytes per flow")
+    if fd_out_t is None:
+        fd_out_t = torch.empty(16 * max(nslots, 1), dtype=torch.uint8, device=base_t.device)
+    elif fd_out_t.numel() * fd_out_t.element_size() < 16 * nslots:
+        raise ValueError("fd_out_t: 16 bytes per slot")
+    s = stream or torch.cuda.current_stream(base_t.device)
+    _check(_lib.lvlip_rtx_dev(flows_t.data_ptr(), lro_res_t.data_ptr() if lro_res_t is not None else None,
+                              snd_t.data_ptr(), snd_res_t.data_ptr() if snd_res_t is not None else None, nflows,
+                              nslots, base_t.data_ptr(), fd_t.data_ptr(), fd_out_t.data_ptr(), s.cuda_stream),
+           "lvlip_rtx_dev")
+    return fd_out_t[:16 * nslots]
 
 
 # ----------------------------------------------------- Group 4: several GPUs --

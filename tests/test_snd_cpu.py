@@ -1,0 +1,691 @@
+"""The ACK side and the retransmit (include/lvlip_skb.h, lvlip_snd_* and
+lvlip_rtx_*) without a GPU: the CPU forms against what the reference's own
+stack left in its socket after each of twelve ACKs and against the frame its
+retransmission timer sent (tests/golden/snd_ref.json, written by
+tests/golden/make_snd_golden.py from the unmodified stack), against an
+independent Python model over random batches and hand-written queues, against
+the reference's frame-by-frame steps restated in Python (reference_steps),
+order independence, the plan and its refusals, the refusals of the CPU and
+device forms, the re-sent frames against lvlip_tso_cpu, a sanitizer build of
+examples/snd_loop.c, and the kernels' scratch size.
+
+The model (model_snd, model_rtx) restates src/tcp_input.c:330-350 and :66-92
+mod 2^32 with struct.unpack on the ring's bytes; the frames a retransmit must
+leave come from lvlip_tso_cpu run with a template that carries the new ack_seq
+and window.  tests/test_snd_gpu.py shares both, with the cases."""
+import ctypes
+import functools
+import json
+import os
+import re
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import lvlip
+from test_ack_cpu import make_flows, template_hdr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "snd_ref.json")
+CANARY = 0x5A
+M32 = 0xFFFFFFFF
+GUARD = 64
+ELIGIBLE = (lvlip.LRO_PLACED, lvlip.LRO_NO_DATA, lvlip.LRO_OUT_OF_WINDOW)
+STATUSES = (1, 2, 3, 4, 5, 6, 7, 8, 9, 16, 17, 18, 19, 20, 21)
+
+
+# --------------------------------------------------------------- the model --
+
+def frame_end_seq(ring: np.ndarray, off: int) -> int:
+    """seq + dlen of the frame at ring[off:], from its 54 header bytes."""
+    h = ring[off:off + 54].tobytes()
+    iplen, = struct.unpack_from("!H", h, 16)
+    seq, = struct.unpack_from("!I", h, 38)
+    return (seq + iplen - 4 * (h[14] & 15) - 4 * (h[46] >> 4)) & M32
+
+
+def model_snd(flows, snd, rec, ring, fd) -> np.ndarray:
+    """One SND_RESULT_DTYPE per flow from the header's text: the classes of
+    src/tcp_input.c:330-350 against snd_una at entry, mod 2^32, and the
+    leading run of tcp_clean_rto_queue (:72-84)."""
+    res = np.zeros(flows.size, dtype=lvlip.SND_RESULT_DTYPE)
+    for r in rec:
+        k = int(r["flow"])
+        if k >= flows.size or int(r["status"]) not in ELIGIBLE or not int(r["tcp_flags"]) & 0x10:
+            continue
+        if int(r["rel"]) > int(flows[k]["rcv_wnd"]):
+            continue
+        una, nxt = int(snd[k]["snd_una"]), int(snd[k]["snd_nxt"])
+        d, span = (int(r["ack_seq"]) - una) & M32, (nxt - una) & M32
+        if 1 <= d <= span:
+            res[k]["n_new"] += 1
+            res[k]["acked"] = max(int(res[k]["acked"]), d)
+        elif d == 0:
+            res[k]["n_dup"] += 1
+        elif d >= 1 << 31:
+            res[k]["n_old"] += 1
+        else:
+            res[k]["n_beyond"] += 1
+    for k in range(flows.size):
+        una, acked = int(snd[k]["snd_una"]), int(res[k]["acked"])
+        res[k]["snd_una"] = (una + acked) & M32
+        p = 0
+        while p < int(snd[k]["nseg"]):
+            d = fd[int(snd[k]["seg0"]) + p]
+            if int(d["len"]) < 54 or (frame_end_seq(ring, int(d["offset"])) - una) & M32 > acked:
+                break
+            p += 1
+        res[k]["popped"], res[k]["inflight"] = p, int(snd[k]["nseg"]) - p
+    return res
+
+
+def model_rtx(case, lro_res, snd_res, ring_before: np.ndarray):
+    """(ring, fd_out) a retransmit must leave: every live frame as
+    lvlip_tso_cpu builds it from a template with the new ack_seq and window,
+    every other byte of the ring as it was."""
+    sends = case.sends.copy()
+    for i, k in enumerate(case.send_flow):
+        ack = (int(case.flows[k]["rcv_nxt"]) + (int(lro_res[k]["delivered"]) if lro_res is not None else 0)) & M32
+        sends[i]["hdr"][42:46] = np.frombuffer(struct.pack("!I", ack), dtype=np.uint8)
+        sends[i]["hdr"][48:50] = np.frombuffer(struct.pack("!H", int(case.snd[k]["win"])), dtype=np.uint8)
+    resent, fd2 = lvlip.tso_cpu(case.payload, sends, out=np.full(ring_before.size, CANARY, dtype=np.uint8))
+    assert np.array_equal(fd2, case.fd_tso)
+    want = ring_before.copy()
+    nslots = int(case.snd["rtx"].sum())
+    fd_out = np.zeros(nslots, dtype=lvlip.FRAME_DESC_DTYPE)
+    for k in range(case.flows.size):
+        s = case.snd[k]
+        popped = int(snd_res[k]["popped"]) if snd_res is not None else 0
+        for j in range(int(s["rtx"])):
+            if popped + j >= int(s["nseg"]):
+                continue
+            d = case.fd[int(s["seg0"]) + popped + j]
+            o, n = int(d["offset"]), int(d["len"])
+            want[o:o + n] = resent[o:o + n]
+            fd_out[int(s["slot0"]) + j] = d
+    return want, fd_out
+
+
+# --------------------------------------------------------------- the cases --
+
+class Case:
+    """nflows planned flows (the REVERSE direction: the peer's ACKs) and, for
+    each, a write queue of nseg[k] frames of mss[k] payload bytes cut by
+    lvlip_tso_cpu into one canary-filled ring at strides of 1 mod 16, so that
+    16 frames of a queue start at every residue mod 16; snd_una[k] is the first frame's
+    seq."""
+
+    def __init__(self, nseg, mss, una=None, rtx=None, seed=0, span=None):
+        n = len(nseg)
+        rng = np.random.default_rng(seed)
+        self.flows = make_flows(n)
+        self.una = [(0xFFFFFC00 + 0x10203 * k) & M32 if una is None else una[k] for k in range(n)]
+        self.send_flow = [k for k in range(n) if nseg[k]]
+        sends, off, poff = [], 3, 0
+        for k in self.send_flow:
+            length = (nseg[k] - 1) * mss[k] + 1 + (k * 7) % mss[k]
+            stride = 54 + mss[k] + ((1 - 54 - mss[k]) % 16 or 16)  # 1 mod 16: 16 frames in a row, 16 residues
+            sends.append(lvlip.tso_send(template_hdr(self.flows[k], seq=self.una[k], flags=0x18), poff, length, mss[k],
+                                        out_off=off, stride=stride))
+            off += nseg[k] * stride + (k % 2)
+            poff += length
+        self.sends = np.concatenate(sends) if sends else np.zeros(0, dtype=lvlip.TsoSend)
+        self.payload = rng.integers(0, 256, max(poff, 1), dtype=np.uint8)
+        total, out_bytes = lvlip.tso_plan(self.sends)
+        self.ring, self.fd_tso = lvlip.tso_cpu(self.payload, self.sends,
+                                               out=np.full(out_bytes + GUARD, CANARY, dtype=np.uint8))
+        self.fd = self.fd_tso.copy()
+        self.snd = np.zeros(n, dtype=lvlip.SND_FLOW_DTYPE)
+        for i, k in enumerate(self.send_flow):
+            self.snd[k]["seg0"], self.snd[k]["nseg"] = int(self.sends[i]["seg0"]), nseg[k]
+            self.snd[k]["snd_nxt"] = int(self.sends[i]["len"])
+        self.snd["snd_una"] = self.una
+        self.snd["snd_nxt"] = (self.snd["snd_nxt"].astype(np.uint64) + self.snd["snd_una"]) & M32
+        if span is not None:
+            self.snd["snd_nxt"] = (self.snd["snd_una"].astype(np.uint64) + np.asarray(span, dtype=np.uint64)) & M32
+        self.snd["rtx"] = 2 if rtx is None else rtx
+        self.snd["win"] = (0x1234 + 257 * np.arange(n)) & 0xFFFF
+        self.nslots, self.nfd = lvlip.snd_plan(self.snd)
+        assert self.nfd <= total
+
+    def span(self, k):
+        return (int(self.snd[k]["snd_nxt"]) - int(self.snd[k]["snd_una"])) & M32
+
+
+def make_records(case: Case, n: int, seed: int, one_flow=None, few_flows=False) -> np.ndarray:
+    """n records as lvlip_lro_* could leave them, in no order: every status
+    (only three count), ACK flag set and clear, rel at and just beyond the
+    window, ack_seq old, equal to snd_una, in mid-segment, on a boundary, equal
+    to snd_nxt and beyond it."""
+    rng = np.random.default_rng(seed)
+    nflows = case.flows.size
+    rec = np.zeros(n, dtype=lvlip.LRO_REC_DTYPE)
+    for i in range(n):
+        if one_flow is not None:
+            k = one_flow
+        elif few_flows:
+            k = int(rng.integers(0, min(nflows, 3)))
+        else:
+            k = int(rng.integers(0, nflows))
+        una, span, wnd = int(case.snd[k]["snd_una"]), case.span(k), int(case.flows[k]["rcv_wnd"])
+        kind = int(rng.integers(0, 8))
+        d = (-int(rng.integers(1, 5000)) if kind == 0 else 0 if kind == 1 else int(rng.integers(0, span + 1)) if kind < 5
+             else span if kind == 5 else span + int(rng.integers(1, 3000)) if kind == 6 else int(rng.integers(0, 1 << 32)))
+        status = STATUSES[int(rng.integers(0, len(STATUSES)))] if rng.integers(0, 3) == 0 else ELIGIBLE[i % 3]
+        rel = (0, wnd, wnd + 1, int(rng.integers(0, wnd)))[int(rng.integers(0, 4))]
+        flags = 0x10 | int(rng.integers(0, 2)) * 0x08 if rng.integers(0, 6) else 0x08
+        flow = k if rng.integers(0, 20) else (M32, nflows, nflows + 7)[i % 3]  # no flow of the plan: ignored
+        rec[i] = (flow, rel, int(rng.integers(0, 1461)), status, flags, (una + d) & M32)
+    return rec
+
+
+@functools.lru_cache(maxsize=None)
+def hand() -> Case:
+    """Flow 0: snd_una 12 bytes below 2^32, so that d and every end_seq wrap.
+    1: a span of 0 over a queue of one.  2: no queue.  3: a queue of one.
+    4: the second frame in front of the first.  5-10: one payload size each."""
+    c = Case(nseg=[5, 1, 0, 1, 4, 3, 3, 17, 3, 3, 2], mss=[536, 100, 1, 536, 536, 1, 2, 3, 536, 1460, 8946],
+             una=[0xFFFFFFF4, 7, 9, 0x80000000, 0x7FFFFF00, 1, 2, 3, 0xFFFFFE00, 5, 6], seed=3)
+    c.snd[1]["snd_nxt"] = c.snd[1]["snd_una"]
+    q = int(c.snd[4]["seg0"])
+    c.fd[[q, q + 1]] = c.fd[[q + 1, q]]
+    assert sorted({int(o) % 16 for o in c.fd["offset"]}) == list(range(16))
+    return c
+
+
+def _rec(flow, ack_seq, status=lvlip.LRO_NO_DATA, flags=0x10, rel=0, dlen=0):
+    r = np.zeros(1, dtype=lvlip.LRO_REC_DTYPE)
+    r[0] = (flow, rel, dlen, status, flags, ack_seq & M32)
+    return r
+
+
+def _fields(r):
+    return {n: int(r[n]) for n in lvlip.SND_RESULT_DTYPE.names}
+
+
+# ---------------------------------------------------------------- the layout --
+
+def test_layout():
+    assert lvlip.SND_FLOW_DTYPE.itemsize == 32 and lvlip.SND_RESULT_DTYPE.itemsize == 32
+    src = open(os.path.join(ROOT, "include", "lvlip_skb.h")).read()
+    for name, dt in (("lvlip_snd_flow", lvlip.SND_FLOW_DTYPE), ("lvlip_snd_result", lvlip.SND_RESULT_DTYPE)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src, flags=re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        fields = [f.strip() for decl in body.split(";") for f in re.sub(r"uint\d+_t", "", decl).split(",") if f.strip()]
+        assert fields == list(dt.names), name
+    prog = ('#include <stdio.h>\n#include "lvlip_skb.h"\nint main(void){printf("%zu %zu %zu %zu\\n", sizeof(lvlip_snd_flow),'
+            'sizeof(lvlip_snd_result), __builtin_offsetof(lvlip_snd_flow, win), __builtin_offsetof(lvlip_snd_result, popped));}')
+    exe = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"snd_layout_{os.getpid()}")
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=prog, text=True, check=True)
+    try:
+        assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split() == ["32", "32", "24", "24"]
+    finally:
+        os.unlink(exe)
+    for name in ("lvlip_snd_plan", "lvlip_snd_cpu", "lvlip_snd_dev", "lvlip_rtx_cpu", "lvlip_rtx_dev"):
+        assert getattr(lvlip.lib(), name).argtypes == lvlip.SIGNATURES[name][1]
+    assert lvlip.lib().lvlip_abi_version() == 2
+
+
+# ------------------------------------------------------------ the ACK side --
+
+def test_the_named_cases():
+    """What the calls say about each edge case, spelled out, so that the
+    model comparison below is not vacuous."""
+    c = hand()
+    snd = lambda rec: lvlip.snd_cpu(c.flows, c.snd, rec, c.ring, c.fd)  # noqa: E731
+    # flow 0: snd_una = 2^32 - 12, segments of 536: the first ends at 524
+    una = 0xFFFFFFF4
+    r = snd(_rec(0, una + 536))[0]
+    assert _fields(r) == dict(snd_una=524, acked=536, n_new=1, n_dup=0, n_old=0, n_beyond=0, popped=1, inflight=4)
+    r = snd(_rec(0, una + 536 + 300))[0]  # mid-segment: nothing beyond the boundary is popped
+    assert (int(r["acked"]), int(r["popped"]), int(r["snd_una"])) == (836, 1, 824)
+    r = snd(_rec(0, una + 535))[0]
+    assert (int(r["n_new"]), int(r["popped"])) == (1, 0)
+    r = snd(_rec(0, int(c.snd[0]["snd_nxt"])))[0]  # everything
+    assert (int(r["popped"]), int(r["inflight"]), int(r["snd_una"])) == (5, 0, int(c.snd[0]["snd_nxt"]))
+    r = snd(np.concatenate([_rec(0, una), _rec(0, una - 1), _rec(0, int(c.snd[0]["snd_nxt"]) + 1)]))[0]
+    assert _fields(r) == dict(snd_una=una, acked=0, n_new=0, n_dup=1, n_old=1, n_beyond=1, popped=0, inflight=5)
+    # eligibility: the window's edge, the flag, the statuses
+    wnd = int(c.flows[0]["rcv_wnd"])
+    assert int(snd(_rec(0, una + 536, rel=wnd))[0]["n_new"]) == 1
+    assert int(snd(_rec(0, una + 536, rel=wnd + 1))[0]["n_new"]) == 0
+    assert int(snd(_rec(0, una + 536, flags=0x08))[0]["n_new"]) == 0
+    for st in STATUSES:
+        assert int(snd(_rec(0, una + 536, status=st))[0]["n_new"]) == (st in ELIGIBLE), st
+    # flow 1: span 0: snd_una itself is a duplicate, one more is beyond
+    r = snd(np.concatenate([_rec(1, 7), _rec(1, 8)]))[1]
+    assert (int(r["n_dup"]), int(r["n_beyond"]), int(r["n_new"]), int(r["popped"])) == (1, 1, 0, 0)
+    # flow 2: no queue; flow 3: a queue of one
+    r = snd(_rec(2, 9))[2]
+    assert (int(r["popped"]), int(r["inflight"])) == (0, 0)
+    r = snd(_rec(3, int(c.snd[3]["snd_nxt"])))[3]
+    assert (int(r["popped"]), int(r["inflight"]), int(r["n_new"])) == (1, 0, 1)
+    # flow 4: the queue's first entry is the stream's second segment: acknowledging the first pops nothing
+    r = snd(_rec(4, 0x7FFFFF00 + 536))[4]
+    assert (int(r["n_new"]), int(r["acked"]), int(r["popped"]), int(r["inflight"])) == (1, 536, 0, 4)
+    r = snd(_rec(4, 0x7FFFFF00 + 1072))[4]
+    assert int(r["popped"]) == 2
+
+
+@pytest.mark.parametrize("seed", range(4))
+def test_snd_cpu_equals_model(seed):
+    c = hand()
+    rec = make_records(c, 400, seed)
+    want = model_snd(c.flows, c.snd, rec, c.ring, c.fd)
+    before = [a.copy() for a in (c.flows, c.snd, rec, c.ring, c.fd)]
+    got = lvlip.snd_cpu(c.flows, c.snd, rec, c.ring, c.fd)
+    assert got.tobytes() == want.tobytes(), [(k, _fields(got[k]), _fields(want[k])) for k in range(got.size)
+                                             if got[k] != want[k]][:3]
+    for a, b in zip((c.flows, c.snd, rec, c.ring, c.fd), before):
+        assert np.array_equal(a, b), "only res is written"
+    assert (want["n_new"] > 0).any() and (want["n_dup"] > 0).any() and (want["n_old"] > 0).any()
+    assert (want["n_beyond"] > 0).any() and (want["popped"] > 0).any()
+    assert want[4]["n_new"] > 0  # the out-of-order queue was acknowledged
+
+
+def test_order_independence():
+    c = hand()
+    rec = make_records(c, 300, 9)
+    want = lvlip.snd_cpu(c.flows, c.snd, rec, c.ring, c.fd).tobytes()
+    rng = np.random.default_rng(1)
+    for _ in range(3):
+        assert lvlip.snd_cpu(c.flows, c.snd, rec[rng.permutation(rec.size)], c.ring, c.fd).tobytes() == want
+    assert lvlip.snd_cpu(c.flows, c.snd, np.concatenate([rec, rec]), c.ring, c.fd)["acked"].tobytes() == \
+        np.frombuffer(want, dtype=lvlip.SND_RESULT_DTYPE)["acked"].tobytes()
+
+
+def reference_steps(una: int, nxt: int, ends, acks):
+    """src/tcp_input.c:330-350 and :66-92 frame by frame, as the reference
+    runs them (running snd_una; plain comparisons, valid while nothing
+    wraps).  Returns (snd_una, frames popped)."""
+    popped = 0
+    for a in acks:
+        if una < a <= nxt:
+            una = a
+            while popped < len(ends) and ends[popped] <= una:
+                popped += 1
+    return una, popped
+
+
+def test_final_state_is_the_reference_order_by_order():
+    """The final snd_una and popped are what frame-by-frame processing
+    leaves, whatever the arrival order."""
+    c = Case(nseg=[6], mss=[536], una=[1000])
+    ends = [frame_end_seq(c.ring, int(d["offset"])) for d in c.fd]
+    nxt = int(c.snd[0]["snd_nxt"])
+    rng = np.random.default_rng(5)
+    for _ in range(20):
+        acks = [int(a) for a in rng.integers(900, nxt + 50, 7)]
+        una, popped = reference_steps(1000, nxt, ends, acks)
+        r = lvlip.snd_cpu(c.flows, c.snd, np.concatenate([_rec(0, a) for a in acks]), c.ring, c.fd)[0]
+        assert (int(r["snd_una"]), int(r["popped"])) == (una, popped), acks
+
+
+# ------------------------------------------------------------------ golden --
+
+@functools.lru_cache(maxsize=None)
+def fixture():
+    with open(GOLDEN) as f:
+        return json.load(f)
+
+
+def golden_ring(fx):
+    """(flow, ring, fd): the reference's four data frames in a ring at four
+    alignments, and the reverse flow that parses the peer's ACKs."""
+    frames = [bytes.fromhex(h) for h in fx["queue"]]
+    f0 = frames[0]
+    sport, dport = struct.unpack_from("!HH", f0, 34)
+    flow = lvlip.lro_flow(f0[30:34], f0[26:30], dport, sport, fx["rcv_nxt"], fx["resend"]["rcv_wnd"])
+    lvlip.lro_plan(flow)
+    ring, fd = lvlip.pack_frames(frames, align_mod=16, seed=2)
+    ring = np.concatenate([np.ascontiguousarray(ring).view(np.uint8).reshape(-1), np.zeros(GUARD, dtype=np.uint8)])
+    return flow, ring, np.ascontiguousarray(fd, dtype=lvlip.FRAME_DESC_DTYPE)
+
+
+def golden_snd(state, rtx=0, win=0):
+    """The send side of the reference's socket in `state`: its write queue is
+    the last state['queue'] of the four frames."""
+    snd = np.zeros(1, dtype=lvlip.SND_FLOW_DTYPE)
+    snd[0]["snd_una"], snd[0]["snd_nxt"] = state["snd_una"], state["snd_nxt"]
+    snd[0]["seg0"], snd[0]["nseg"], snd[0]["rtx"], snd[0]["win"] = 4 - state["queue"], state["queue"], rtx, win
+    lvlip.snd_plan(snd)
+    return snd
+
+
+GOLDEN_CLASS = {"old": "n_old", "snd_una": "n_dup", "beyond": "n_beyond", "mid_segment": "n_new", "boundary": "n_new",
+                "snd_nxt": "n_new"}
+
+
+def test_fixture_holds_the_cases():
+    """What the golden tests rest on: six cases in each stage, a queue of four
+    with three still unsent in stage A, a re-sent head with a moved rcv_nxt."""
+    fx = fixture()
+    for stage in "AB":
+        assert {c["name"] for c in fx["cases"] if c["stage"] == stage} == set(GOLDEN_CLASS)
+    assert [len(q) // 2 - 54 for q in fx["queue"]] == [536, 536, 536, 393]
+    popped = [c["before"]["queue"] - c["after"]["queue"] for c in fx["cases"]]
+    assert set(popped) == {0, 1, 2} and all(c["before"]["queue"] == 4 for c in fx["cases"] if c["stage"] == "A")
+    r = fx["resend"]
+    assert r["index"] == 2 and r["rcv_nxt"] == fx["rcv_nxt"] + 100 and len(r["frame"]) // 2 == 54 + 536
+
+
+def golden_cases():
+    return [(c["stage"], c["name"]) for c in fixture()["cases"]]
+
+
+@pytest.mark.parametrize("stage,name", golden_cases())
+def test_snd_cpu_reproduces_the_reference_queue(stage, name):
+    """One pure ACK fed to the reference's stack, from the state it was in:
+    the snd_una and the queue length it was left with, and the class."""
+    fx = fixture()
+    c = next(c for c in fx["cases"] if (c["stage"], c["name"]) == (stage, name))
+    flow, ring, fd = golden_ring(fx)
+    r = lvlip.snd_cpu(flow, golden_snd(c["before"]), _rec(0, c["ack_seq"]), ring, fd)[0]
+    assert int(r["snd_una"]) == c["after"]["snd_una"]
+    assert int(r["inflight"]) == c["after"]["queue"] and int(r["popped"]) == c["before"]["queue"] - c["after"]["queue"]
+    counts = {k: int(r[k]) for k in ("n_new", "n_dup", "n_old", "n_beyond")}
+    assert counts == {k: int(k == GOLDEN_CLASS[name]) for k in counts}
+
+
+def test_snd_cpu_reproduces_the_reference_stage_by_stage():
+    """All of a stage's ACKs as ONE batch, in the order fed and reversed: the
+    snd_una and the queue the reference ended the stage with."""
+    fx = fixture()
+    flow, ring, fd = golden_ring(fx)
+    for stage in "AB":
+        cs = [c for c in fx["cases"] if c["stage"] == stage]
+        rec = np.concatenate([_rec(0, c["ack_seq"]) for c in cs])
+        for batch in (rec, rec[::-1].copy()):
+            r = lvlip.snd_cpu(flow, golden_snd(cs[0]["before"]), batch, ring, fd)[0]
+            assert int(r["snd_una"]) == cs[-1]["after"]["snd_una"], stage
+            assert int(r["inflight"]) == cs[-1]["after"]["queue"], stage
+
+
+def golden_resend(fx):
+    """(flow, lro result, snd, ring, fd, the frame's offset, the reference's
+    bytes) of the retransmission the reference's timer sent."""
+    flow, ring, fd = golden_ring(fx)
+    r = fx["resend"]
+    lro = np.zeros(1, dtype=lvlip.LRO_RESULT_DTYPE)
+    lro[0]["delivered"] = (r["rcv_nxt"] - fx["rcv_nxt"]) & M32
+    snd = golden_snd(r["state"], rtx=1, win=r["rcv_wnd"])
+    return flow, lro, snd, ring, fd, int(fd[r["index"]]["offset"]), bytes.fromhex(r["frame"])
+
+
+def test_rtx_cpu_reproduces_the_reference_resend():
+    """The head of the queue as tcp_retransmission_timeout sent it after
+    in-order data had moved rcv_nxt: every byte, seq included (the timer
+    passes snd_una, the head's own seq), from the frame as first sent."""
+    flow, lro, snd, ring, fd, o, want = golden_resend(fixture())
+    before = ring.copy()
+    assert before[o:o + len(want)].tobytes() != want
+    fd_out = lvlip.rtx_cpu(flow, lro, snd, None, ring, fd)
+    assert (int(fd_out[0]["offset"]), int(fd_out[0]["len"])) == (o, len(want))
+    assert ring[o:o + len(want)].tobytes().hex() == want.hex()
+    changed = np.flatnonzero(ring != before)
+    assert changed.size and set(int(v) for v in changed - o) <= set(range(42, 46)) | set(range(48, 52))
+
+
+# ------------------------------------------------------------------ the plan --
+
+def _plan(s, n=None):
+    nfd = ctypes.c_uint32(7)
+    return lvlip.lib().lvlip_snd_plan(s.ctypes.data, s.size if n is None else n, ctypes.byref(nfd)), nfd.value
+
+
+def _base():
+    s = np.zeros(3, dtype=lvlip.SND_FLOW_DTYPE)
+    s["snd_una"], s["snd_nxt"] = (10, 0xFFFFFF00, 5), (10 + (1 << 30), 0x100, 5)
+    s["seg0"], s["nseg"], s["rtx"] = (0, 10, 14), (10, 4, 6), (1, 0, 3)
+    return s
+
+
+PLAN_REFUSALS = {
+    "reserved": lambda s: s["reserved"].__setitem__(1, 1),
+    "reserved2": lambda s: s["reserved2"].__setitem__(2, 0x100),
+    "span_above_2^30": lambda s: s["snd_nxt"].__setitem__(0, 11 + (1 << 30)),
+    "snd_nxt_behind_snd_una": lambda s: s["snd_nxt"].__setitem__(2, 4),
+    "queues_overlap": lambda s: s["seg0"].__setitem__(1, 9),
+    "queue_inside_another": lambda s: (s["seg0"].__setitem__(2, 3), s["nseg"].__setitem__(2, 2)),
+    "queue_wraps": lambda s: (s["seg0"].__setitem__(2, 0xFFFFFFFE), s["nseg"].__setitem__(2, 2)),
+    "nseg_total": lambda s: (s["seg0"].__setitem__(slice(None), (0, 0x7FFFFFFF, 0)),
+                             s["nseg"].__setitem__(slice(None), (0x7FFFFFFF, 0x7FFFFFFF, 0))),
+    "rtx_total": lambda s: s["rtx"].__setitem__(slice(None), (0x80000000, 0x7FFFFFF1, 0)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PLAN_REFUSALS))
+def test_plan_refusals(name):
+    s = _base()
+    assert _plan(s) == (4, 20)
+    PLAN_REFUSALS[name](s)
+    s["slot0"] = 77
+    before = s.copy()
+    assert _plan(s) == (0xFFFFFFFF, 0), name
+    assert np.array_equal(s, before), "a refused plan modifies nothing"
+    with pytest.raises(ValueError):
+        lvlip.snd_plan(s)
+
+
+def test_plan_refuses_too_many_flows():
+    s = np.zeros(65537, dtype=lvlip.SND_FLOW_DTYPE)
+    assert _plan(s) == (0xFFFFFFFF, 0)
+    assert _plan(s, 65536) == (0, 0)
+
+
+def test_plan_accepts_and_fills_slot0():
+    L = lvlip.lib()
+    s = _base()
+    s["slot0"] = 99
+    before = s.copy()
+    assert _plan(s) == (4, 20)
+    assert s["slot0"].tolist() == [0, 1, 1]
+    before["slot0"] = s["slot0"]
+    assert np.array_equal(s, before), "slot0 is all the plan writes"
+    s["seg0"] = (14, 0, 10)  # any order; queues that abut
+    s["nseg"] = (6, 10, 4)
+    assert _plan(s) == (4, 20)
+    s["nseg"][1] = 0  # an empty queue overlaps nothing, wherever it says it is
+    s["seg0"][1] = 15
+    assert _plan(s) == (4, 20)
+    s["rtx"] = (0xFFFFFFF0, 0, 0)  # LVLIP_MAX_BATCH itself
+    assert _plan(s)[0] == 0xFFFFFFF0
+    assert L.lvlip_snd_plan(s.ctypes.data, 3, None) == 0xFFFFFFF0
+    assert L.lvlip_snd_plan(None, 0, None) == 0
+    assert L.lvlip_snd_plan(None, 3, None) == 0xFFFFFFFF
+
+
+# ------------------------------------------------------------- the refusals --
+
+def _aligned(a: np.ndarray, align: int = 16):
+    """(keep-alive buffer, address): a's bytes at an aligned address."""
+    raw = a.view(np.uint8).reshape(-1)
+    buf = np.zeros(raw.size + align, dtype=np.uint8)
+    p = buf.ctypes.data + (-buf.ctypes.data % align)
+    ctypes.memmove(p, raw.ctypes.data, raw.size)
+    return buf, p
+
+
+def test_cpu_and_dev_refusals_without_gpu():
+    """Refused before anything is written, and for the device forms before any
+    HIP call, so this runs without a device (host memory stands in for the
+    device pointers)."""
+    L = lvlip.lib()
+    c = hand()
+    n = c.flows.size
+    rec = make_records(c, 32, 0)
+    keep = [_aligned(a) for a in (c.flows, c.snd, rec, c.fd)]
+    f, s, r, d = (p for _, p in keep)
+    resbuf = np.full(32 * n + 16, CANARY, dtype=np.uint8)
+    o = resbuf.ctypes.data + (-resbuf.ctypes.data % 16)
+    ring = c.ring.copy()
+    b = ring.ctypes.data
+    snd_both = {"NULL f": (None, s, n, r, 32, b, d, o), "NULL s": (f, None, n, r, 32, b, d, o),
+                "NULL rec": (f, s, n, None, 32, b, d, o), "NULL base": (f, s, n, r, 32, None, d, o),
+                "NULL fd": (f, s, n, r, 32, b, None, o), "NULL res": (f, s, n, r, 32, b, d, None),
+                "n above LVLIP_MAX_BATCH": (f, s, n, r, 0xFFFFFFF1, b, d, o),
+                "nflows above LVLIP_LRO_MAX_FLOWS": (f, s, 65537, r, 32, b, d, o)}
+    for what, args in snd_both.items():
+        assert L.lvlip_snd_cpu(*args) == lvlip.EINVAL, what
+        assert L.lvlip_snd_dev(*args, None) == lvlip.EINVAL, what
+    snd_dev_only = {"f at 4 mod 8": (f + 4, s, n, r, 32, b, d, o), "s at 4 mod 8": (f, s + 4, n, r, 32, b, d, o),
+                    "rec at 8 mod 16": (f, s, n, r + 8, 32, b, d, o), "fd at 8 mod 16": (f, s, n, r, 32, b, d + 8, o),
+                    "res at 8 mod 16": (f, s, n, r, 32, b, d, o + 8)}
+    for what, args in snd_dev_only.items():
+        assert L.lvlip_snd_dev(*args, None) == lvlip.EINVAL, what
+    # no records, no flows: nothing to do, nothing written, whatever else is passed
+    for args in ((f, s, n, r, 0, b, d, o), (f, s, 0, r, 32, b, d, o), (None, None, 0, None, 0, None, None, None),
+                 (None, None, n, None, 0, None, None, None)):
+        assert L.lvlip_snd_cpu(*args) == lvlip.OK
+        assert L.lvlip_snd_dev(*args, None) == lvlip.OK
+    assert (resbuf == CANARY).all()
+
+    ns = c.nslots
+    outbuf = np.full(16 * ns + 16, CANARY, dtype=np.uint8)
+    fo = outbuf.ctypes.data + (-outbuf.ctypes.data % 16)
+    lro = np.zeros(n, dtype=lvlip.LRO_RESULT_DTYPE)
+    sres = np.zeros(n, dtype=lvlip.SND_RESULT_DTYPE)
+    keep2 = [_aligned(a) for a in (lro, sres)]
+    lr, sr = (p for _, p in keep2)
+    rtx_both = {"NULL f": (None, lr, s, sr, n, ns, b, d, fo), "NULL s": (f, lr, None, sr, n, ns, b, d, fo),
+                "NULL base": (f, lr, s, sr, n, ns, None, d, fo), "NULL fd": (f, lr, s, sr, n, ns, b, None, fo),
+                "NULL fd_out": (f, lr, s, sr, n, ns, b, d, None), "no flows": (f, lr, s, sr, 0, ns, b, d, fo),
+                "nflows above LVLIP_LRO_MAX_FLOWS": (f, lr, s, sr, 65537, ns, b, d, fo),
+                "nslots above LVLIP_MAX_BATCH": (f, lr, s, sr, n, 0xFFFFFFF1, b, d, fo)}
+    for what, args in rtx_both.items():
+        assert L.lvlip_rtx_cpu(*args) == lvlip.EINVAL, what
+        assert L.lvlip_rtx_dev(*args, None) == lvlip.EINVAL, what
+    for what, args in {"one slot too many": (f, lr, s, sr, n, ns + 1, b, d, fo),
+                       "one slot too few": (f, lr, s, sr, n, ns - 1, b, d, fo)}.items():
+        assert L.lvlip_rtx_cpu(*args) == lvlip.EINVAL, what
+    rtx_dev_only = {"f at 4 mod 8": (f + 4, lr, s, sr, n, ns, b, d, fo), "s at 4 mod 8": (f, lr, s + 4, sr, n, ns, b, d, fo),
+                    "lro at 8 mod 16": (f, lr + 8, s, sr, n, ns, b, d, fo),
+                    "snd at 8 mod 16": (f, lr, s, sr + 8, n, ns, b, d, fo),
+                    "fd at 8 mod 16": (f, lr, s, sr, n, ns, b, d + 8, fo),
+                    "fd_out at 8 mod 16": (f, lr, s, sr, n, ns, b, d, fo + 8)}
+    for what, args in rtx_dev_only.items():
+        assert L.lvlip_rtx_dev(*args, None) == lvlip.EINVAL, what
+    assert L.lvlip_rtx_cpu(None, None, None, None, 0, 0, None, None, None) == lvlip.OK
+    assert L.lvlip_rtx_dev(None, None, None, None, 0, 0, None, None, None, None) == lvlip.OK
+    assert L.lvlip_rtx_cpu(f, lr, s, sr, n, 0, b, d, fo) == lvlip.OK
+    assert (outbuf == CANARY).all() and np.array_equal(ring, c.ring)
+
+
+# ----------------------------------------------------------- the retransmit --
+
+def rtx_inputs(c: Case, seed: int):
+    """(lro results, snd results) for a retransmit: delivered random, popped
+    0 .. nseg so that live, partly live and dead slots all occur."""
+    rng = np.random.default_rng(seed)
+    lro = np.zeros(c.flows.size, dtype=lvlip.LRO_RESULT_DTYPE)
+    lro["delivered"] = rng.integers(0, 1 << 32, c.flows.size, dtype=np.uint64).astype(np.uint32)
+    sres = np.zeros(c.flows.size, dtype=lvlip.SND_RESULT_DTYPE)
+    sres["popped"] = [int(rng.integers(0, int(n) + 1)) for n in c.snd["nseg"]]
+    return lro, sres
+
+
+@pytest.mark.parametrize("with_results", (True, False))
+def test_rtx_cpu_equals_tso_with_the_new_fields(with_results):
+    """Every re-sent frame is what lvlip_tso_cpu builds from a template with
+    the new ack_seq and window; dead slots are {0, 0, 0}; no other byte of
+    the ring changes (canaries between the frames, all 16 alignments)."""
+    c = Case(nseg=[5, 1, 0, 1, 4, 3, 3, 17, 3, 3, 2], mss=[536, 100, 1, 536, 536, 1, 2, 3, 536, 1460, 8946],
+             rtx=[2, 3, 2, 1, 4, 3, 2, 17, 0, 3, 2], seed=8)
+    q7 = int(c.snd[7]["seg0"])
+    assert sorted(int(o) % 16 for o in c.fd["offset"][q7:q7 + 16]) == list(range(16))
+    lro, sres = rtx_inputs(c, 4) if with_results else (None, None)
+    sres_in = None
+    if with_results:
+        sres["popped"][:5] = (3, 0, 0, 1, 1)  # slots past the queue's end, and a queue already empty
+        sres["popped"][7] = 0
+        sres_in = sres
+    ring = c.ring.copy()
+    want, want_fd = model_rtx(c, lro, sres_in, ring)
+    snd_before = c.snd.copy()
+    fd_out = lvlip.rtx_cpu(c.flows, lro, c.snd, sres_in, ring, c.fd)
+    assert np.array_equal(fd_out, want_fd)
+    if not np.array_equal(ring, want):
+        bad = np.flatnonzero(ring != want)
+        pytest.fail(f"{bad.size} ring bytes differ, first at {int(bad[0])}")
+    dead = int((want_fd["len"] == 0).sum())
+    assert 0 < dead < want_fd.size and (want_fd[want_fd["len"] == 0]["offset"] == 0).all()
+    assert np.array_equal(c.snd, snd_before) and not np.array_equal(ring, c.ring)
+    # the re-sent frames verify as a receiver verifies them
+    live = want_fd[want_fd["len"] > 0]
+    _, rec = lvlip.lro_cpu(ring, live, np.zeros(0, dtype=lvlip.LRO_FLOW_DTYPE), lvlip.RX_VERIFY_L4,
+                           out=np.zeros(1, dtype=np.uint8))
+    assert (rec["status"] == lvlip.LRO_NO_FLOW).all()
+
+
+def test_rtx_cpu_leaves_frames_it_cannot_rewrite():
+    """A queue entry that is no IPv4/TCP frame of the ring's kind is a dead
+    slot, and its bytes stay."""
+    c = Case(nseg=[4], mss=[100], rtx=[4], seed=2)
+    ring = c.ring.copy()
+    fd = c.fd.copy()
+    fd[0]["len"] = 53
+    ring[int(fd[1]["offset"]) + 14] = 0x46
+    ring[int(fd[2]["offset"]) + 17] += 1  # ip.len one beyond the frame
+    before = ring.copy()
+    fd_out = lvlip.rtx_cpu(c.flows, None, c.snd, None, ring, fd)
+    assert fd_out["len"].tolist() == [0, 0, 0, int(fd[3]["len"])]
+    changed = np.flatnonzero(ring != before)
+    assert changed.size and changed.min() >= int(fd[3]["offset"]) + 42 and changed.max() <= int(fd[3]["offset"]) + 51
+
+
+def test_pseudo_header_carry_is_lost_and_depends_on_the_payload():
+    """Addresses whose u32 sum wraps: the field is the reference's (the carry
+    lost, src/tcp.c:92-95), which the full recomputation reproduces."""
+    saddr, daddr = bytes((254, 255, 255, 255)), bytes((7, 0, 0, 128))
+    c = Case.__new__(Case)
+    flows = make_flows(1, addr=(saddr, daddr))
+    hdr = template_hdr(flows[0], seq=77, flags=0x18)
+    pay = np.arange(600, dtype=np.uint32).astype(np.uint8)
+    sends = lvlip.tso_send(hdr, 0, 600, 536, out_off=1)
+    ring, fd = lvlip.tso_cpu(pay, sends)
+    snd = np.zeros(1, dtype=lvlip.SND_FLOW_DTYPE)
+    snd[0]["snd_una"], snd[0]["snd_nxt"], snd[0]["nseg"], snd[0]["rtx"], snd[0]["win"] = 77, 677, 2, 2, 999
+    lvlip.snd_plan(snd)
+    c.flows, c.snd, c.sends, c.send_flow, c.payload, c.fd, c.fd_tso = flows, snd, sends, [0], pay, fd, fd
+    want, want_fd = model_rtx(c, None, None, ring)
+    got = ring.copy()
+    assert np.array_equal(lvlip.rtx_cpu(flows, None, snd, None, got, fd), want_fd)
+    assert np.array_equal(got, want) and not np.array_equal(got, ring)
+
+
+# ------------------------------------------------ the example and the kernels --
+
+def test_example_under_sanitizers(tmp_path):
+    """examples/snd_loop.c (its own main: the whole loop with loss and
+    recovery on the CPU forms, every buffer malloc'd at exactly its planned
+    size) compiled with the library's C sources under ASan + UBSan, and run as
+    a program."""
+    exe = tmp_path / "snd_loop_san"
+    src = [os.path.join(ROOT, "examples", "snd_loop.c")] + [
+        os.path.join(ROOT, "level-ip_amd", "csrc", f)
+        for f in ("snd_cpu.c", "ack_cpu.c", "rcv_cpu.c", "seg_cpu.c", "csum_cpu.c")]
+    subprocess.run(["gcc", "-std=c99", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror",
+                    "-I", os.path.join(ROOT, "include"), *src, "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "snd_loop ok" in r.stdout and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+def test_kernels_use_no_scratch(tmp_path):
+    """k_rtx keeps the header's 16 dwords and its sweeps in registers with
+    constant indices; k_snd_rec and k_snd_fin hold a few words: every
+    kernel's private segment is 0."""
+    asm = tmp_path / "snd_kernels.s"
+    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-I", os.path.join(ROOT, "include"),
+                    "-S", "--cuda-device-only", os.path.join(ROOT, "level-ip_amd", "csrc", "snd_kernels.hip"),
+                    "-o", str(asm)], check=True, capture_output=True)
+    text = asm.read_text()
+    kernels = re.findall(r"\.name:\s+(\S*k_(?:snd_rec|snd_fin|rtx)\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)",
+                         text)
+    assert sorted(re.search(r"k_(snd_rec|snd_fin|rtx)", name).group(0) for name, _ in kernels) == \
+        ["k_rtx", "k_snd_fin", "k_snd_rec"], kernels
+    assert all(int(size) == 0 for _, size in kernels), kernels
