@@ -298,8 +298,9 @@ int lvlip_tso_cpu(const void *payload, const lvlip_tso_send *s, uint32_t n, void
  * device pointers, of any alignment for payload and out (s: 8 B, fd: 16 B);
  * s as lvlip_tso_plan left it, nseg what it returned.  n == 0 is a no-op;
  * NULL payload, s or out with n > 0, or nseg 0 or above LVLIP_MAX_BATCH, is
- * LVLIP_EINVAL before any HIP call.  The device does not validate the
- * templates again: the caller planned the sends. */
+ * LVLIP_EINVAL before any HIP call; LVLIP_ENODEV without a device; a failed
+ * launch is LVLIP_EHIP (lvlip_last_hip_error).  The device does not validate
+ * the templates again: the caller planned the sends. */
 int lvlip_tso_dev(const void *payload, const lvlip_tso_send *s, uint32_t n, uint32_t nseg,
                   void *out, lvlip_frame_desc *fd, void *stream);
 
@@ -419,7 +420,8 @@ int lvlip_lro_cpu(const void *base, const lvlip_frame_desc *fd, uint32_t n, cons
  * to the last frame's end rounded up to 16 B), fd and rec 16-B aligned, f 8-B
  * aligned, out any alignment.  n == 0 is a no-op; the refusals of
  * lvlip_lro_cpu are LVLIP_EINVAL before any HIP call, except the flows' order,
- * which the device does not check: the caller planned them. */
+ * which the device does not check: the caller planned them.  LVLIP_ENODEV
+ * without a device; a failed launch is LVLIP_EHIP (lvlip_last_hip_error). */
 int lvlip_lro_dev(const void *base, const lvlip_frame_desc *fd, uint32_t n, const lvlip_lro_flow *f,
                   uint32_t nflows, uint32_t flags, void *out, lvlip_lro_rec *rec, void *stream);
 

@@ -8,53 +8,21 @@
  * src/ip_output.c:14-56), with the template standing for the socket's state
  * and the flow's lvlip_lro_result for rcv_nxt and the SACK list.
  */
-#include <stddef.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
+#include "tcp_hdr.h"
 
-#include "lvlip_skb.h"
-
-#define ACK_HDR 54u /* Ethernet 14 + IPv4 20 + TCP 20 */
+#define ACK_HDR TCP_FRAME_HDR
 #define NONE 0xFFFFFFFFu
-
-static inline uint32_t le32(const uint8_t *p)
-{
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
-
-static inline void put_be32(uint8_t *p, uint32_t v)
-{
-    p[0] = (uint8_t)(v >> 24);
-    p[1] = (uint8_t)(v >> 16);
-    p[2] = (uint8_t)(v >> 8);
-    p[3] = (uint8_t)v;
-}
-
-static inline uint16_t bswap16(uint16_t x) { return (uint16_t)((x << 8) | (x >> 8)); }
 
 /* ------------------------------------------------------------------ plan -- */
 
 static int tmpl_ok(const lvlip_ack_tmpl *t, const lvlip_lro_flow *f)
 {
     const uint8_t *h = t->hdr;
-    if (t->max_sack > 4u || t->reserved != 0) return 0;
-    if (h[12] != 0x08 || h[13] != 0x00) return 0; /* ethertype IPv4 */
-    if (h[14] != 0x45) return 0;                  /* version 4, ihl 5 */
-    if (h[23] != 6) return 0;                     /* IP_TCP */
-    if ((h[46] >> 4) != 5) return 0;              /* TCP header length, no options */
+    if (t->max_sack > 4u || t->reserved != 0 || !tcp_tmpl_ok(h)) return 0;
     /* the reverse of the flow: what the peer sends from is where the ACK goes */
     if (memcmp(h + 26, &f->daddr, 4) != 0 || memcmp(h + 30, &f->saddr, 4) != 0) return 0;
     if (memcmp(h + 34, &f->dport, 2) != 0 || memcmp(h + 36, &f->sport, 2) != 0) return 0;
     return t->out_off <= UINT64_MAX - LVLIP_ACK_MAX_FRAME;
-}
-
-static int off_cmp(const void *a, const void *b)
-{
-    const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
-    return x < y ? -1 : x > y;
 }
 
 uint32_t lvlip_ack_plan(const lvlip_ack_tmpl *t, const lvlip_lro_flow *f, uint32_t nflows, uint64_t *out_bytes)
@@ -67,15 +35,16 @@ uint32_t lvlip_ack_plan(const lvlip_ack_tmpl *t, const lvlip_lro_flow *f, uint32
         if (!tmpl_ok(&t[k], &f[k])) return NONE;
         if (t[k].out_off + LVLIP_ACK_MAX_FRAME > top) top = t[k].out_off + LVLIP_ACK_MAX_FRAME;
     }
-    /* the slots, sorted by start: each must end before the next begins */
-    uint64_t *r = malloc((size_t)nflows * sizeof *r);
+    /* no two slots [out_off, out_off + LVLIP_ACK_MAX_FRAME) may overlap */
+    uint64_t *r = malloc((size_t)nflows * 2u * sizeof *r);
     if (!r) return NONE;
-    for (uint32_t k = 0; k < nflows; k++) r[k] = t[k].out_off;
-    qsort(r, nflows, sizeof *r, off_cmp);
-    int bad = 0;
-    for (uint32_t k = 1; k < nflows && !bad; k++) bad = r[k] - r[k - 1u] < LVLIP_ACK_MAX_FRAME;
+    for (uint32_t k = 0; k < nflows; k++) {
+        r[2u * k] = t[k].out_off;
+        r[2u * k + 1u] = t[k].out_off + LVLIP_ACK_MAX_FRAME;
+    }
+    const int ok = ranges_disjoint(r, nflows);
     free(r);
-    if (bad) return NONE;
+    if (!ok) return NONE;
     if (out_bytes) *out_bytes = top;
     return nflows;
 }
@@ -102,10 +71,9 @@ int lvlip_ack_cpu(const lvlip_ack_tmpl *t, const lvlip_lro_flow *f, const lvlip_
         uint8_t *ih = p + 14, *th = p + 34;
         memcpy(p, t[k].hdr, ACK_HDR);
         /* tcp_send_ack: hl (src/tcp_output.c:261); tcp_transmit_skb: ack_seq,
-         * csum 0, the options (:107,110,113-115) */
+         * the options (:107,113-115) */
         put_be32(th + 8, f[k].rcv_nxt + res[k].delivered);
         th[12] = (uint8_t)(((5u + optlen / 4u) << 4) | (th[12] & 0x0fu));
-        th[16] = th[17] = 0;
         if (b) {
             /* tcp_write_options, src/tcp_output.c:71-86: the last block first */
             uint8_t *o = th + 20;
@@ -116,19 +84,8 @@ int lvlip_ack_cpu(const lvlip_ack_tmpl *t, const lvlip_lro_flow *f, const lvlip_
                 put_be32(o + 4, res[k].sack[i].right);
             }
         }
-        /* ip_output: len, csum 0, then ip_send_check (src/ip_output.c:35,42,53) */
-        const uint16_t iplen = (uint16_t)(40u + optlen);
-        ih[2] = (uint8_t)(iplen >> 8);
-        ih[3] = (uint8_t)iplen;
-        ih[10] = ih[11] = 0;
-        const uint16_t ic = checksum(ih, 20, 0);
-        memcpy(ih + 10, &ic, 2);
-        /* tcp_v4_checksum, src/tcp_output.c:126; src/tcp.c:92-95: u32 adds,
-         * the carry out of bit 31 is lost */
-        const uint16_t l4 = (uint16_t)(20u + optlen);
-        const uint32_t seed = le32(ih + 12) + le32(ih + 16) + bswap16(6) + bswap16(l4);
-        const uint16_t tc = checksum(th, (int)l4, (int)seed);
-        memcpy(th + 16, &tc, 2);
+        ip_output_tail(ih, 40u + optlen);
+        tcp_csum_tail(ih, th, 20u + optlen);
         if (fd) fd[k].offset = off, fd[k].len = ACK_HDR + optlen, fd[k].reserved = 0;
     }
     return LVLIP_OK;

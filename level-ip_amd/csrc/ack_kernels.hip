@@ -17,7 +17,7 @@
 //
 // The frame in registers.  Dwords h[0..13] are the template's 54 bytes (the
 // top half of h[13] is replaced), patched as tcp_transmit_skb and ip_output
-// patch them (seg_kernels.hip does the same for data segments).  The option
+// patch them (tcp_hdr_dev.h; k_tso does the same for data segments).  The option
 // starts at byte 54 = 2 mod 4, so its nine dwords ow[0..8] (01 01 05 len, then
 // left and right of each block in network order, zero beyond the b blocks
 // written) straddle the frame's dwords: frame dword 13 is urp | ow[0] << 16
@@ -27,8 +27,9 @@
 //
 // Which block goes where (sack[b-1-i] at position i, b known only at run time)
 // and which 16 bytes a lane keeps (chunk c at frame offset 16 c - (F & 15))
-// are selected with compare masks over registers with constant indices, never
-// with a runtime index into an array, which hipcc would put in scratch.
+// are selected with compare masks over registers with constant indices
+// (ack_sel4 here, hdr_chunk in tcp_hdr_dev.h), never with a runtime index into
+// an array, which hipcc would put in scratch.
 // Chunks the frame covers whole leave as one 16-B store; the first and the
 // last leave as the dwords and bytes inside [F, F + 54 + optlen) and nothing
 // else (store_chunk, row_copy.h), so the rest of a 90-byte slot and an abutting
@@ -41,32 +42,17 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 
 #include "csum_dev.h"
 #include "row_copy.h"
+#include "tcp_hdr_dev.h"
 
 namespace lvlip {
 
 constexpr uint32_t ACK_GROUP = 8;                  // lanes per flow
 constexpr uint32_t ACK_FLOWS = 256 / ACK_GROUP;    // flows per workgroup
-constexpr int ACK_HDR = 54;                        // Ethernet 14 + IPv4 20 + TCP 20
+constexpr int ACK_HDR = TCP_FRAME_HDR;
 constexpr int ACK_BLOCKS = 6;                      // 16-B blocks of the frame's 23 dwords
-
-// block j - 1 of blk[] (zeros for j == 0 and j > ACK_BLOCKS): masks, not a
-// select chain, which hipcc turns into a table in scratch
-__device__ __forceinline__ uint4 ack_pick(uint32_t j, const uint4 (&blk)[ACK_BLOCKS]) {
-    uint4 r = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (int i = 0; i < ACK_BLOCKS; ++i) {
-        const uint32_t m = j == (uint32_t)i + 1u ? ~0u : 0u;
-        r.x |= blk[i].x & m;
-        r.y |= blk[i].y & m;
-        r.z |= blk[i].z & m;
-        r.w |= blk[i].w & m;
-    }
-    return r;
-}
 
 // a[j] for j = 0 .. 3, 0 beyond
 __device__ __forceinline__ uint32_t ack_sel4(uint32_t j, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3) {
@@ -113,23 +99,19 @@ __global__ __launch_bounds__(256) void k_ack(const lvlip_ack_tmpl* t, const lvli
     }
 
     // ---- the 54 header bytes
-    h[4] = (h[4] & 0xffff0000u) | bswap16u(40u + optlen);         // ip.len, src/ip_output.c:35,46
+    h[4] = (h[4] & 0xffff0000u) | bswap16u(40u + optlen);       // ip.len, src/ip_output.c:35,46
     h[6] &= 0xffff0000u;                                          // ip.csum = 0, src/ip_output.c:42
     const uint32_t ipw = (h[3] >> 16) + halves(h[4]) + halves(h[5]) + halves(h[6]) + halves(h[7]) +
                          (h[8] & 0xffffu);
     h[6] |= (uint32_t)finish(0u, ipw);                            // ip_send_check, src/ip_output.c:8-12
-    const uint32_t ack = __builtin_bswap32(rcv_nxt + r0.x);       // src/tcp_output.c:107,122
-    h[10] = (h[10] & 0xffffu) | (ack << 16);
-    h[11] = (h[11] & 0xff0f0000u) | (ack >> 16) | ((5u + optlen / 4u) << 20);  // hl, src/tcp_output.c:261
+    hdr_put_ack(h, __builtin_bswap32(rcv_nxt + r0.x));
+    h[11] = (h[11] & 0xff0fffffu) | ((5u + optlen / 4u) << 20);   // hl, src/tcp_output.c:261
     h[12] &= 0xffffu;                                             // tcp.csum = 0, src/tcp_output.c:110
     h[13] = (h[13] & 0xffffu) | (ow[0] << 16);                    // urp, then the option's first two bytes
-    uint32_t thw = (h[8] >> 16) + halves(h[9]) + halves(h[10]) + halves(h[11]) + halves(h[12]) + (h[13] & 0xffffu);
+    uint32_t thw = hdr_tcp_words(h);
 #pragma unroll
     for (int i = 0; i < 9; ++i) thw += halves(ow[i]);
-    const uint32_t saddr = (h[6] >> 16) | (h[7] << 16), daddr = (h[7] >> 16) | (h[8] << 16);
-    // src/tcp.c:92-95: u32 adds, the carry out of bit 31 is lost
-    const uint32_t seed = saddr + daddr + 0x0600u + bswap16u(20u + optlen);
-    h[12] |= (uint32_t)finish(seed, thw) << 16;                   // src/tcp_output.c:126
+    h[12] |= (uint32_t)finish(hdr_tcp_seed(h, 20u + optlen), thw) << 16;  // src/tcp_output.c:126
 
     // ---- the frame's dwords as six 16-B blocks; dword 13 + i = ow[i-1] >> 16 | ow[i] << 16
     uint32_t w[10];  // frame dwords 14 .. 23 (22 ends the longest frame; 23 is zero)
@@ -141,30 +123,20 @@ __global__ __launch_bounds__(256) void k_ack(const lvlip_ack_tmpl* t, const lvli
                                    make_uint4(h[8], h[9], h[10], h[11]), make_uint4(h[12], h[13], w[0], w[1]),
                                    make_uint4(w[2], w[3], w[4], w[5]),   make_uint4(w[6], w[7], w[8], w[9])};
 
-    // ---- destination chunk c holds bytes [16 c + 16 - fo, 16 c + 32 - fo) of
-    // {16 zero bytes, the frame, zeros}
+    // ---- lane c keeps destination chunk c
     const uint64_t F = reinterpret_cast<uint64_t>(out) + off;  // the frame's first byte
     const int fo = (int)(F & 15ull);
     const uint64_t D = F - (uint64_t)fo;
     const uint32_t nch = acked ? (uint32_t)(fo + L + 15) >> 4 : 0u;  // chunks the frame touches: 4 .. 7
-    if (c < nch) {
-        const uint4 nx = ack_pick(c + 1u, blk);
-        const uint4 cu = fo == 0 ? nx : ack_pick(c, blk);
-        const uint4 v = funnel16(cu, nx, (uint32_t)(16 - fo) & 15u);
-        store_chunk(D + 16ull * c, v, c == 0u ? fo : 0, min(16, fo + L - (int)(16u * c)));
-    }
-    if (fd && live && c == 0u) {
-        typedef __attribute__((address_space(1))) u32x4 gvec;
-        *reinterpret_cast<gvec*>(reinterpret_cast<uint64_t>(fd + g)) =
-            u32x4{(uint32_t)off, (uint32_t)(off >> 32), acked ? (uint32_t)L : 0u, 0u};
-    }
+    if (c < nch) store_chunk(D + 16ull * c, hdr_chunk(c, fo, blk), c == 0u ? fo : 0, min(16, fo + L - (int)(16u * c)));
+    if (fd && live && c == 0u)
+        store_global(reinterpret_cast<uint64_t>(fd + g),
+                     u32x4{(uint32_t)off, (uint32_t)(off >> 32), acked ? (uint32_t)L : 0u, 0u});
 }
 
 }  // namespace lvlip
 
 extern "C" {
-
-void lvlip_set_last_hip_error(const char* msg);  // csum_kernels.hip (hidden)
 
 int lvlip_ack_dev(const lvlip_ack_tmpl* t, const lvlip_lro_flow* f, const lvlip_lro_result* res, uint32_t nflows,
                   uint32_t flags, void* out, lvlip_frame_desc* fd, void* stream) {
@@ -176,15 +148,7 @@ int lvlip_ack_dev(const lvlip_ack_tmpl* t, const lvlip_lro_flow* f, const lvlip_
     const uint32_t grid = (nflows + lvlip::ACK_FLOWS - 1u) / lvlip::ACK_FLOWS;
     hipLaunchKernelGGL(lvlip::k_ack, dim3(grid), dim3(256), 0, (hipStream_t)stream, t, f, res, nflows, flags,
                        (uint8_t*)out, fd);
-    const hipError_t e = hipGetLastError();
-    if (e == hipErrorNoDevice) return LVLIP_ENODEV;
-    if (e != hipSuccess) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "k_ack: %s", hipGetErrorString(e));
-        lvlip_set_last_hip_error(msg);
-        return LVLIP_EHIP;
-    }
-    return LVLIP_OK;
+    return lvlip_launch_status(hipGetLastError(), "k_ack");
 }
 
 }  // extern "C"

@@ -43,11 +43,11 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "lvlip_skb.h"
+#include "tcp_hdr_dev.h"  // lvlip_launch_status
 
 namespace lvlip {
 
@@ -283,21 +283,12 @@ static bool adv_plan(uint32_t n, adv_layout& L) {
 
 extern "C" {
 
-void lvlip_set_last_hip_error(const char* msg);  // csum_kernels.hip (hidden)
-
 size_t lvlip_lro_advance_workspace_bytes(uint32_t n, uint32_t /*nflows*/) {
     if (n == 0 || n > LVLIP_MAX_BATCH) return 0;
     int devices = 0;
     if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) return 0;
     lvlip::adv_layout L;
     return lvlip::adv_plan(n, L) ? L.total : 0;
-}
-
-static int adv_fail(const char* what, hipError_t e) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-    lvlip_set_last_hip_error(msg);
-    return LVLIP_EHIP;
 }
 
 int lvlip_lro_advance_dev(const lvlip_lro_flow* f, uint32_t nflows, const lvlip_lro_rec* rec, uint32_t n,
@@ -310,8 +301,8 @@ int lvlip_lro_advance_dev(const lvlip_lro_flow* f, uint32_t nflows, const lvlip_
     if (n && (!workspace || ((uintptr_t)workspace & 255u))) return LVLIP_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
-        const hipError_t e = hipMemsetAsync(res, 0, (size_t)nflows * sizeof *res, s);
-        return e == hipSuccess ? LVLIP_OK : adv_fail("lvlip_lro_advance_dev: hipMemsetAsync", e);
+        return lvlip_launch_status(hipMemsetAsync(res, 0, (size_t)nflows * sizeof *res, s),
+                                   "lvlip_lro_advance_dev: hipMemsetAsync");
     }
     adv_layout L;
     if (!adv_plan(n, L)) return LVLIP_ENODEV;
@@ -327,24 +318,24 @@ int lvlip_lro_advance_dev(const lvlip_lro_flow* f, uint32_t nflows, const lvlip_
 
     hipLaunchKernelGGL(k_adv_keys, dim3(ntiles), dim3(ADV_TILE), 0, s, rec, n, nflows, keys.current(),
                        lens.current());
-    if ((e = hipGetLastError()) != hipSuccess) return adv_fail("k_adv_keys", e);
+    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_adv_keys");
     size_t tmp_bytes = L.tmp_bytes;
     if ((e = adv_sort(ws + L.tmp, tmp_bytes, keys, lens, n, s)) != hipSuccess)
-        return adv_fail("lvlip_lro_advance_dev: radix sort", e);
+        return lvlip_launch_status(e, "lvlip_lro_advance_dev: radix sort");
     const uint64_t* sorted = keys.current();
     const uint16_t* slen = lens.current();
     uint64_t* H = keys.alternate();  // the sort is done with it
     hipLaunchKernelGGL(k_adv_reduce, dim3(ntiles), dim3(ADV_TILE), 0, s, sorted, slen, n, agg);
-    if ((e = hipGetLastError()) != hipSuccess) return adv_fail("k_adv_reduce", e);
+    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_adv_reduce");
     hipLaunchKernelGGL(k_adv_spine, dim3(1), dim3(ADV_SPINE), 0, s, agg, ntiles);
-    if ((e = hipGetLastError()) != hipSuccess) return adv_fail("k_adv_spine", e);
+    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_adv_spine");
     hipLaunchKernelGGL(k_adv_heads, dim3(ntiles), dim3(ADV_TILE), 0, s, sorted, slen, n, (const uint64_t*)agg, H,
                        bitmap);
-    if ((e = hipGetLastError()) != hipSuccess) return adv_fail("k_adv_heads", e);
+    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_adv_heads");
     const uint32_t egrid = (uint32_t)(((uint64_t)nflows + 3u) / 4u);
     hipLaunchKernelGGL(k_adv_emit, dim3(egrid), dim3(256), 0, s, f, nflows, sorted, (const uint64_t*)H,
                        (const uint64_t*)bitmap, n, res);
-    if ((e = hipGetLastError()) != hipSuccess) return adv_fail("k_adv_emit", e);
+    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_adv_emit");
     return LVLIP_OK;
 }
 

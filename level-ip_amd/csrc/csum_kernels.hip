@@ -457,6 +457,15 @@ const char* lvlip_last_hip_error(void) { return g_last_err; }
 // calling thread.
 void lvlip_set_last_hip_error(const char* msg) { snprintf(g_last_err, sizeof g_last_err, "%s", msg ? msg : ""); }
 
+// Hidden (tcp_hdr_dev.h): the return code of a device call of the TCP path
+// (seg, rcv, adv, ack, snd _kernels.hip) for the status of its launch or of a
+// step it put on the stream; a failure's text is left for lvlip_last_hip_error().
+int lvlip_launch_status(hipError_t e, const char* what) {
+    if (e == hipSuccess) return LVLIP_OK;
+    if (e == hipErrorNoDevice) return LVLIP_ENODEV;
+    return hip_fail(e, what);
+}
+
 // Hidden: loads this file's code object on the current device (every product
 // kernel is in it), so a context's first call does not pay the load inside
 // its first launch (~2 ms, measured as the first 64-frame call's time outside

@@ -9,12 +9,7 @@
  * tcp_data_dequeue (:49-85) do per skb, with a planned flow standing for the
  * socket's tcb.
  */
-#include <stddef.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "lvlip_skb.h"
+#include "tcp_hdr.h"
 
 #define ETH_HDR_LEN 14u
 #define PROTO_ICMP 1u
@@ -24,35 +19,15 @@
 
 static inline uint32_t be16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
 
-static inline uint32_t be32(const uint8_t *p)
-{
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-static inline uint32_t le32(const uint8_t *p)
-{
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
-
-static inline uint32_t bswap16(uint32_t x) { return ((x & 0xffu) << 8) | ((x >> 8) & 0xffu); }
-
-/* lvlip_pseudo_sum_rfc (skb_batch.c): the pseudo header as 16-bit halves */
+/* lvlip_pseudo_sum_rfc (skb_batch.c): the pseudo header as 16-bit halves; len is at most 65535 */
 static inline uint32_t pseudo_rfc(uint32_t s, uint32_t d, uint32_t proto, uint32_t len)
 {
-    return (s & 0xffffu) + (s >> 16) + (d & 0xffffu) + (d >> 16) + bswap16(proto) + bswap16(len);
+    return (s & 0xffffu) + (s >> 16) + (d & 0xffffu) + (d >> 16) + bswap16((uint16_t)proto) + bswap16((uint16_t)len);
 }
 
 /* ------------------------------------------------------------------ plan -- */
 
 static int key_cmp(const void *a, const void *b) { return memcmp(a, b, 12); }
-
-static int range_cmp(const void *a, const void *b)
-{
-    const uint64_t x = ((const uint64_t *)a)[0], y = ((const uint64_t *)b)[0];
-    return x < y ? -1 : x > y;
-}
 
 uint32_t lvlip_lro_plan(lvlip_lro_flow *f, uint32_t n, uint64_t *out_bytes)
 {
@@ -68,16 +43,14 @@ uint32_t lvlip_lro_plan(lvlip_lro_flow *f, uint32_t n, uint64_t *out_bytes)
         const uint64_t end = f[k].out_off + f[k].rcv_wnd;
         if (end > top) top = end;
     }
-    /* the ranges, sorted by start: each must end before the next begins */
+    /* no two ranges [out_off, out_off + rcv_wnd) may overlap */
     uint64_t *r = malloc((size_t)n * 2u * sizeof *r);
     if (!r) return NONE;
     for (uint32_t k = 0; k < n; k++) {
         r[2u * k] = f[k].out_off;
         r[2u * k + 1u] = f[k].out_off + f[k].rcv_wnd;
     }
-    qsort(r, n, 2u * sizeof *r, range_cmp);
-    int bad = 0;
-    for (uint32_t k = 1; k < n && !bad; k++) bad = r[2u * k - 1u] > r[2u * k];
+    int bad = !ranges_disjoint(r, n);
     free(r);
     if (bad) return NONE;
     /* a duplicate key shows as equal neighbours after the sort; the flows are

@@ -1,7 +1,8 @@
 // rcv_kernels.hip — TCP receive coalescing on the device (include/lvlip_skb.h,
 // "f1 on the device: receive coalescing"): frames in HBM -> each payload at its
 // place in its flow's byte stream, one record per frame.  k_tso
-// (seg_kernels.hip) run backwards, out of the same pieces (row_copy.h);
+// (seg_kernels.hip) run backwards, out of the same pieces (row_copy.h, and
+// tcp_hdr_dev.h for the record's store);
 // rcv_cpu.c is the same on the calling thread, bit for bit.
 //
 // Work mapping.  One DPP row (16 lanes) per frame, four frames per wave, 16
@@ -41,11 +42,11 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 
 #include "csum_dev.h"
 #include "flat_src.h"
 #include "row_copy.h"
+#include "tcp_hdr_dev.h"
 
 namespace lvlip {
 
@@ -252,18 +253,15 @@ __global__ __launch_bounds__(256) void k_lro(const uint8_t* base, const lvlip_fr
     if (st == 0u) st = st2;
 
     if (live && tl == 0u) {
-        typedef __attribute__((address_space(1))) u32x4 gvec;
         const bool tcp = st == LVLIP_LRO_PLACED || st >= LVLIP_LRO_NO_FLOW;  // the TCP fields mean something
-        *reinterpret_cast<gvec*>(reinterpret_cast<uint64_t>(rec + g)) =
-            tcp ? u32x4{flow, rel, dlen | (st << 16) | (tflags << 24), ack} : u32x4{LRO_NONE, 0u, st << 16, 0u};
+        store_global(reinterpret_cast<uint64_t>(rec + g), tcp ? u32x4{flow, rel, dlen | (st << 16) | (tflags << 24), ack}
+                                                              : u32x4{LRO_NONE, 0u, st << 16, 0u});
     }
 }
 
 }  // namespace lvlip
 
 extern "C" {
-
-void lvlip_set_last_hip_error(const char* msg);  // csum_kernels.hip (hidden)
 
 int lvlip_lro_dev(const void* base, const lvlip_frame_desc* fd, uint32_t n, const lvlip_lro_flow* f,
                   uint32_t nflows, uint32_t flags, void* out, lvlip_lro_rec* rec, void* stream) {
@@ -277,14 +275,7 @@ int lvlip_lro_dev(const void* base, const lvlip_frame_desc* fd, uint32_t n, cons
     else
         hipLaunchKernelGGL(lvlip::k_lro<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)base,
                            fd, n, f, nflows, (uint8_t*)out, rec);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "k_lro: %s", hipGetErrorString(e));
-        lvlip_set_last_hip_error(msg);
-        return LVLIP_EHIP;
-    }
-    return LVLIP_OK;
+    return lvlip_launch_status(hipGetLastError(), "k_lro");
 }
 
 }  // extern "C"

@@ -7,40 +7,17 @@
  * tcp_transmit_skb, src/tcp_output.c:93-129 -> ip_output,
  * src/ip_output.c:14-56), with the template standing for the socket's state.
  */
-#include <stddef.h>
-#include <stdint.h>
-#include <string.h>
+#include "tcp_hdr.h"
 
-#include "lvlip_skb.h"
-
-#define TSO_HDR 54u       /* Ethernet 14 + IPv4 20 + TCP 20 */
+#define TSO_HDR TCP_FRAME_HDR
 #define TSO_MSS_MAX 65495u /* 65535 - 40: the IPv4 total length is 16 bits */
 #define TCP_FIN_PSH 0x09u  /* byte 13 of the TCP header: FIN 0x01, PSH 0x08 */
 
-static inline uint32_t le32(const uint8_t *p)
-{
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
-
-static inline uint32_t be32(const uint8_t *p)
-{
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-static inline uint16_t bswap16(uint16_t x) { return (uint16_t)((x << 8) | (x >> 8)); }
-
 static int send_ok(const lvlip_tso_send *s)
 {
-    const uint8_t *h = s->hdr;
     if (s->len == 0 || s->mss == 0 || s->mss > TSO_MSS_MAX || s->reserved != 0) return 0;
     if (s->stride < TSO_HDR + s->mss) return 0;
-    if (h[12] != 0x08 || h[13] != 0x00) return 0; /* ethertype IPv4 */
-    if (h[14] != 0x45) return 0;                  /* version 4, ihl 5 */
-    if (h[23] != 6) return 0;                     /* IP_TCP */
-    if ((h[46] >> 4) != 5) return 0;              /* TCP header length, no options */
-    return 1;
+    return tcp_tmpl_ok(s->hdr);
 }
 
 static inline uint64_t send_segs(const lvlip_tso_send *s)
@@ -104,28 +81,12 @@ int lvlip_tso_cpu(const void *payload, const lvlip_tso_send *s, uint32_t n, void
             uint8_t *ih = f + 14, *th = f + 34;
             memcpy(f, t->hdr, TSO_HDR);
             memcpy(f + TSO_HDR, src + done, dlen);
-            /* ip_output: len, csum 0, then ip_send_check (src/ip_output.c:35,42,53) */
-            const uint16_t iplen = (uint16_t)(40u + dlen);
-            ih[2] = (uint8_t)(iplen >> 8);
-            ih[3] = (uint8_t)iplen;
-            ih[10] = ih[11] = 0;
-            const uint16_t ic = checksum(ih, 20, 0);
-            memcpy(ih + 10, &ic, 2);
-            /* tcp_transmit_skb: seq, csum 0, then tcp_v4_checksum
-             * (src/tcp_output.c:106,110,126); PSH on the last segment only
-             * (src/tcp_output.c:466), and FIN with it */
-            const uint32_t seq = seq0 + (uint32_t)done;
-            th[4] = (uint8_t)(seq >> 24);
-            th[5] = (uint8_t)(seq >> 16);
-            th[6] = (uint8_t)(seq >> 8);
-            th[7] = (uint8_t)seq;
+            ip_output_tail(ih, 40u + dlen);
+            /* tcp_transmit_skb: seq (src/tcp_output.c:106); PSH on the last
+             * segment only (src/tcp_output.c:466), and FIN with it */
+            put_be32(th + 4, seq0 + (uint32_t)done);
             if (i + 1u != k) th[13] &= (uint8_t)~TCP_FIN_PSH;
-            th[16] = th[17] = 0;
-            const uint16_t l4 = (uint16_t)(20u + dlen);
-            /* src/tcp.c:92-95: u32 adds, the carry out of bit 31 is lost */
-            const uint32_t seed = le32(ih + 12) + le32(ih + 16) + bswap16(6) + bswap16(l4);
-            const uint16_t tc = checksum(th, (int)l4, (int)seed);
-            memcpy(th + 16, &tc, 2);
+            tcp_csum_tail(ih, th, 20u + dlen);
             if (fd) {
                 lvlip_frame_desc *d = &fd[t->seg0 + i];
                 d->offset = off;

@@ -39,35 +39,23 @@
 //
 // The 54 header bytes are built in registers by every lane of the row from
 // the template (14 dwords), patched as tcp_transmit_skb and ip_output patch
-// them; the chunks that hold header bytes (the first 4 or 5) are kept back
+// them (tcp_hdr_dev.h); the chunks that hold header bytes (the first 4 or 5) are kept back
 // until the row's sum is known and then leave with header and payload bytes
 // merged, one store per chunk.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 
 #include "csum_dev.h"
 #include "row_copy.h"
+#include "tcp_hdr_dev.h"
 
 namespace lvlip {
 
 constexpr uint32_t TSO_ROW = 16;                 // lanes per segment
 constexpr uint32_t TSO_SEGS = 256 / TSO_ROW;     // segments per workgroup
 constexpr int TSO_U = 4;                         // sweeps of a row in flight
-constexpr int TSO_HDR = 54;                      // Ethernet 14 + IPv4 20 + TCP 20
-
-__device__ __forceinline__ uint4 pick(uint32_t j, const uint4 a, const uint4 b, const uint4 c,
-                                      const uint4 d) {
-    // block j of {zeros, a, b, c, d, zeros}; masks, not a select chain, which
-    // hipcc turns into a table in scratch
-    const uint32_t ma = j == 1u ? ~0u : 0u, mb = j == 2u ? ~0u : 0u;
-    const uint32_t mc = j == 3u ? ~0u : 0u, md = j == 4u ? ~0u : 0u;
-    return make_uint4((a.x & ma) | (b.x & mb) | (c.x & mc) | (d.x & md),
-                      (a.y & ma) | (b.y & mb) | (c.y & mc) | (d.y & md),
-                      (a.z & ma) | (b.z & mb) | (c.z & mc) | (d.z & md),
-                      (a.w & ma) | (b.w & mb) | (c.w & mc) | (d.w & md));
-}
+constexpr int TSO_HDR = TCP_FRAME_HDR;
 
 __global__ __launch_bounds__(256) void k_tso(const uint8_t* payload, const lvlip_tso_send* s, uint32_t n,
                                              uint32_t nseg, uint8_t* out, lvlip_frame_desc* fd) {
@@ -78,13 +66,7 @@ __global__ __launch_bounds__(256) void k_tso(const uint8_t* payload, const lvlip
 
     // the send of segment g: the last one whose seg0 is <= g (seg0 rises
     // strictly: every send has a segment, and s[0].seg0 == 0)
-    uint32_t slo = 0, shi = n;
-    while (shi - slo > 1u) {
-        const uint32_t mid = slo + (shi - slo) / 2u;
-        if (s[mid].seg0 <= g) slo = mid;
-        else shi = mid;
-    }
-    const lvlip_tso_send* t = s + slo;
+    const lvlip_tso_send* t = s + slot_owner<&lvlip_tso_send::seg0>(s, n, g);
     const uint32_t mss = t->mss, len = t->len;
     const uint32_t i = g - t->seg0;
     const uint64_t done = (uint64_t)i * mss;
@@ -130,7 +112,7 @@ __global__ __launch_bounds__(256) void k_tso(const uint8_t* payload, const lvlip
 
     // ---- the 54 header bytes (every lane of the row the same)
     h[13] &= 0xffffu;                                             // bytes 52-53; the rest is the struct's pad
-    h[4] = (h[4] & 0xffff0000u) | bswap16u(40u + dlen);           // ip.len, src/ip_output.c:35,46
+    h[4] = (h[4] & 0xffff0000u) | bswap16u(40u + dlen);         // ip.len, src/ip_output.c:35,46
     h[6] &= 0xffff0000u;                                          // ip.csum = 0, src/ip_output.c:42
     const uint32_t ipw = (h[3] >> 16) + halves(h[4]) + halves(h[5]) + halves(h[6]) + halves(h[7]) +
                          (h[8] & 0xffffu);
@@ -141,35 +123,24 @@ __global__ __launch_bounds__(256) void k_tso(const uint8_t* payload, const lvlip
     h[10] = (h[10] & 0xffff0000u) | (seq >> 16);
     if (!last) h[11] &= ~(0x09u << 24);                           // FIN, PSH: the last segment's
     h[12] &= 0xffffu;                                             // tcp.csum = 0, src/tcp_output.c:110
-    const uint32_t thw = (h[8] >> 16) + halves(h[9]) + halves(h[10]) + halves(h[11]) + halves(h[12]) + h[13];
-    const uint32_t saddr = (h[6] >> 16) | (h[7] << 16), daddr = (h[7] >> 16) | (h[8] << 16);
-    // src/tcp.c:92-95: u32 adds, the carry out of bit 31 is lost
-    const uint32_t seed = saddr + daddr + 0x0600u + bswap16u(20u + dlen);
-    h[12] |= (uint32_t)finish(seed, thw + W) << 16;               // src/tcp_output.c:126
+    const uint32_t thw = hdr_tcp_words(h);
+    h[12] |= (uint32_t)finish(hdr_tcp_seed(h, 20u + dlen), thw + W) << 16;  // src/tcp_output.c:126
 
-    // ---- the chunks with header bytes: destination chunk k holds bytes
-    // [16 k + 16 - f, 16 k + 32 - f) of {16 zero bytes, the header, zeros}
+    // ---- the chunks with header bytes, merged with the payload bytes kept back
     if (tl < hk && tl < nch) {
-        const uint4 b1 = make_uint4(h[0], h[1], h[2], h[3]), b2 = make_uint4(h[4], h[5], h[6], h[7]);
-        const uint4 b3 = make_uint4(h[8], h[9], h[10], h[11]), b4 = make_uint4(h[12], h[13], 0u, 0u);
-        const uint4 nx = pick(tl + 1u, b1, b2, b3, b4);
-        const uint4 cu = f == 0 ? nx : pick(tl, b1, b2, b3, b4);
-        const uint4 hv = funnel16(cu, nx, (uint32_t)(16 - f) & 15u);
+        const uint4 blk[4] = {make_uint4(h[0], h[1], h[2], h[3]), make_uint4(h[4], h[5], h[6], h[7]),
+                              make_uint4(h[8], h[9], h[10], h[11]), make_uint4(h[12], h[13], 0u, 0u)};
+        const uint4 hv = hdr_chunk(tl, f, blk);
         const uint4 v = make_uint4(keep.x | hv.x, keep.y | hv.y, keep.z | hv.z, keep.w | hv.w);
         store_chunk(D + 16ull * tl, v, tl == 0u ? f : 0, min(16, f + L - (int)(16u * tl)));
     }
-    if (fd && live && tl == 0u) {
-        typedef __attribute__((address_space(1))) u32x4 gvec;
-        *reinterpret_cast<gvec*>(reinterpret_cast<uint64_t>(fd + g)) =
-            u32x4{(uint32_t)off, (uint32_t)(off >> 32), (uint32_t)L, 0u};
-    }
+    if (fd && live && tl == 0u)
+        store_global(reinterpret_cast<uint64_t>(fd + g), u32x4{(uint32_t)off, (uint32_t)(off >> 32), (uint32_t)L, 0u});
 }
 
 }  // namespace lvlip
 
 extern "C" {
-
-void lvlip_set_last_hip_error(const char* msg);  // csum_kernels.hip (hidden)
 
 int lvlip_tso_dev(const void* payload, const lvlip_tso_send* s, uint32_t n, uint32_t nseg, void* out,
                   lvlip_frame_desc* fd, void* stream) {
@@ -178,14 +149,7 @@ int lvlip_tso_dev(const void* payload, const lvlip_tso_send* s, uint32_t n, uint
     const uint32_t grid = (uint32_t)(((uint64_t)nseg + lvlip::TSO_SEGS - 1u) / lvlip::TSO_SEGS);
     hipLaunchKernelGGL(lvlip::k_tso, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)payload, s,
                        n, nseg, (uint8_t*)out, fd);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "k_tso: %s", hipGetErrorString(e));
-        lvlip_set_last_hip_error(msg);
-        return LVLIP_EHIP;
-    }
-    return LVLIP_OK;
+    return lvlip_launch_status(hipGetLastError(), "k_tso");
 }
 
 }  // extern "C"

@@ -10,50 +10,13 @@
  * and tcp_send_next (:198-225) do to a queued segment: tcp_transmit_skb
  * (:93-129) writes ack_seq and the window again and sums the whole segment.
  */
-#include <stddef.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
+#include "tcp_hdr.h"
 
-#include "lvlip_skb.h"
-
-#define SND_HDR 54u /* Ethernet 14 + IPv4 20 + TCP 20 */
+#define SND_HDR TCP_FRAME_HDR
 #define NONE 0xFFFFFFFFu
 #define ACK_FLAG 0x10u
 
-static inline uint32_t le32(const uint8_t *p)
-{
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-}
-
-static inline uint32_t be32(const uint8_t *p)
-{
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-static inline void put_be32(uint8_t *p, uint32_t v)
-{
-    p[0] = (uint8_t)(v >> 24);
-    p[1] = (uint8_t)(v >> 16);
-    p[2] = (uint8_t)(v >> 8);
-    p[3] = (uint8_t)v;
-}
-
-static inline uint16_t bswap16(uint16_t x) { return (uint16_t)((x << 8) | (x >> 8)); }
-
 /* ------------------------------------------------------------------ plan -- */
-
-typedef struct {
-    uint32_t seg0, nseg;
-} queue_range;
-
-static int range_cmp(const void *a, const void *b)
-{
-    const uint32_t x = ((const queue_range *)a)->seg0, y = ((const queue_range *)b)->seg0;
-    return x < y ? -1 : x > y;
-}
 
 uint32_t lvlip_snd_plan(lvlip_snd_flow *s, uint32_t nflows, uint32_t *nfd)
 {
@@ -74,18 +37,20 @@ uint32_t lvlip_snd_plan(lvlip_snd_flow *s, uint32_t nflows, uint32_t *nfd)
         }
     }
     if (segs > LVLIP_MAX_BATCH || slots > LVLIP_MAX_BATCH) return NONE;
-    /* the queues, sorted by their first entry: each must end before the next begins */
+    /* no two queues [seg0, seg0 + nseg) that hold an entry may overlap */
     if (queues > 1u) {
-        queue_range *r = malloc((size_t)queues * sizeof *r);
+        uint64_t *r = malloc((size_t)queues * 2u * sizeof *r);
         if (!r) return NONE;
         uint32_t m = 0;
-        for (uint32_t k = 0; k < nflows; k++)
-            if (s[k].nseg) r[m].seg0 = s[k].seg0, r[m++].nseg = s[k].nseg;
-        qsort(r, m, sizeof *r, range_cmp);
-        int bad = 0;
-        for (uint32_t k = 1; k < m && !bad; k++) bad = r[k].seg0 - r[k - 1u].seg0 < r[k - 1u].nseg;
+        for (uint32_t k = 0; k < nflows; k++) {
+            if (!s[k].nseg) continue;
+            r[2u * m] = s[k].seg0;
+            r[2u * m + 1u] = (uint64_t)s[k].seg0 + s[k].nseg;
+            m++;
+        }
+        const int ok = ranges_disjoint(r, m);
         free(r);
-        if (bad) return NONE;
+        if (!ok) return NONE;
     }
     uint32_t slot = 0;
     for (uint32_t k = 0; k < nflows; k++) {
@@ -169,16 +134,11 @@ int lvlip_rtx_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, const lv
             uint8_t *p = (uint8_t *)base + d.offset, *ih = p + 14, *th = p + 34;
             const uint32_t iplen = ((uint32_t)ih[2] << 8) | ih[3], hl = th[12] >> 4;
             if (ih[0] != 0x45 || 14u + iplen > d.len || hl < 5u || 20u + 4u * hl > iplen) continue;
-            /* tcp_transmit_skb, src/tcp_output.c:107,109,110 and :122,123 */
+            /* tcp_transmit_skb, src/tcp_output.c:107,109 and :122,123 */
             put_be32(th + 8, ack);
             th[14] = (uint8_t)(s[k].win >> 8);
             th[15] = (uint8_t)s[k].win;
-            th[16] = th[17] = 0;
-            /* tcp_v4_checksum, :126; src/tcp.c:92-95: u32 adds, the carry out of bit 31 is lost */
-            const uint16_t l4 = (uint16_t)(iplen - 20u);
-            const uint32_t seed = le32(ih + 12) + le32(ih + 16) + bswap16(6) + bswap16(l4);
-            const uint16_t tc = checksum(th, (int)l4, (int)seed);
-            memcpy(th + 16, &tc, 2);
+            tcp_csum_tail(ih, th, iplen - 20u);
             *o = d;
         }
     }

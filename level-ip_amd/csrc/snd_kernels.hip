@@ -46,7 +46,7 @@
 // request) and funnels them into the frame's dwords h[0..13].  The header is
 // patched in registers as tcp_transmit_skb patches it (ack_seq, win, csum 0,
 // src/tcp_output.c:107-110) and its ten TCP words are summed from the
-// registers; the sweep sums only the bytes behind the header, frame bytes
+// registers (tcp_hdr_dev.h); the sweep sums only the bytes behind the header, frame bytes
 // [54, 14 + ip.len), each read once, masked to the segment at both ends.  The
 // frame's u16 words start at frame byte 34, an even offset, so for a frame at
 // an odd address the two bytes of every aligned u16 are swapped before summing
@@ -73,10 +73,10 @@
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
-#include <stdio.h>
 
 #include "csum_dev.h"
 #include "row_copy.h"
+#include "tcp_hdr_dev.h"
 
 namespace lvlip {
 
@@ -86,22 +86,12 @@ constexpr uint32_t SND_WAVES = 4;                // flows per workgroup of k_snd
 constexpr uint32_t RTX_ROW = 16;                 // lanes per slot
 constexpr uint32_t RTX_SLOTS = 256 / RTX_ROW;    // slots per workgroup
 constexpr int RTX_U = 6;                         // sweeps of a row in flight: an MTU frame in one round
-constexpr int RTX_HDR = 54;                      // Ethernet 14 + IPv4 20 + TCP 20
+constexpr int RTX_HDR = TCP_FRAME_HDR;
 
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
     return v;
-}
-
-// the four bytes at any address a: the one or two aligned dwords that hold them
-__device__ __forceinline__ uint32_t load_u32_any(uint64_t a) {
-    typedef __attribute__((address_space(1))) const uint32_t gdw;
-    const uint64_t a0 = a & ~3ull;
-    const uint32_t r = (uint32_t)(a & 3ull);
-    const uint32_t lo = *reinterpret_cast<gdw*>(a0);
-    const uint32_t hi = r ? *reinterpret_cast<gdw*>(a0 + 4u) : 0u;
-    return __builtin_amdgcn_alignbyte(hi, lo, r);
 }
 
 // ------------------------------------------------------------ the ACK side --
@@ -200,12 +190,7 @@ __global__ __launch_bounds__(256) void k_rtx(const lvlip_lro_flow* f, const lvli
 
     // the flow of slot g: the last one whose slot0 is <= g (slot0 never falls, s[0].slot0 == 0; among
     // flows that share a slot0 only the last has a slot)
-    uint32_t slo = 0, shi = nflows;
-    while (shi - slo > 1u) {
-        const uint32_t mid = slo + (shi - slo) / 2u;
-        if (s[mid].slot0 <= g) slo = mid;
-        else shi = mid;
-    }
+    const uint32_t slo = slot_owner<&lvlip_snd_flow::slot0>(s, nflows, g);
     const lvlip_snd_flow* t = s + slo;
     const uint32_t nseg = t->nseg, j = g - t->slot0;
     const uint32_t popped = snd ? snd[slo].popped : 0u;
@@ -258,17 +243,12 @@ __global__ __launch_bounds__(256) void k_rtx(const lvlip_lro_flow* f, const lvli
 
     // ---- the TCP header as tcp_transmit_skb leaves it (every lane of the row the same)
     const uint32_t rcv_nxt = f[slo].rcv_nxt + (lro ? lro[slo].delivered : 0u);
-    const uint32_t ack = __builtin_bswap32(rcv_nxt);             // src/tcp_output.c:107,122
-    const uint32_t win = bswap16u(t->win);                       // :109,123
-    h[10] = (h[10] & 0xffffu) | (ack << 16);
-    h[11] = (h[11] & 0xffff0000u) | (ack >> 16);
+    const uint32_t ack = __builtin_bswap32(rcv_nxt);
+    const uint32_t win = bswap16u(t->win);                       // src/tcp_output.c:109,123
+    hdr_put_ack(h, ack);
     h[12] = win;                                                 // tcp.csum = 0, :110
-    const uint32_t thw = (h[8] >> 16) + halves(h[9]) + halves(h[10]) + halves(h[11]) + halves(h[12]) +
-                         (h[13] & 0xffffu);
-    const uint32_t saddr = (h[6] >> 16) | (h[7] << 16), daddr = (h[7] >> 16) | (h[8] << 16);
-    // src/tcp.c:92-95: u32 adds, the carry out of bit 31 is lost
-    const uint32_t seed = saddr + daddr + 0x0600u + bswap16u(iplen - 20u);
-    const uint32_t csum = finish(seed, thw + W);                 // :126
+    const uint32_t thw = hdr_tcp_words(h);
+    const uint32_t csum = finish(hdr_tcp_seed(h, iplen - 20u), thw + W);  // :126
 
     // ---- bytes 42-45, 48-49, 50-51: lane tl of the row stores one
     if (live && tl < 8u) {
@@ -277,27 +257,13 @@ __global__ __launch_bounds__(256) void k_rtx(const lvlip_lro_flow* f, const lvli
         const uint32_t at = tl < 4u ? 42u + tl : 44u + tl;
         *reinterpret_cast<gby*>(F + at) = (uint8_t)(word >> (8u * (tl & 3u)));
     }
-    if (inside && tl == 0u) {
-        typedef __attribute__((address_space(1))) u32x4 gvec;
-        *reinterpret_cast<gvec*>(reinterpret_cast<uint64_t>(fd_out + g)) =
-            live ? u32x4{d.x, d.y, d.z, d.w} : u32x4{0u, 0u, 0u, 0u};
-    }
+    if (inside && tl == 0u)
+        store_global(reinterpret_cast<uint64_t>(fd_out + g), live ? u32x4{d.x, d.y, d.z, d.w} : u32x4{0u, 0u, 0u, 0u});
 }
 
 }  // namespace lvlip
 
 extern "C" {
-
-void lvlip_set_last_hip_error(const char* msg);  // csum_kernels.hip (hidden)
-
-static int snd_hip_result(hipError_t e, const char* what) {
-    if (e == hipSuccess) return LVLIP_OK;
-    if (e == hipErrorNoDevice) return LVLIP_ENODEV;
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-    lvlip_set_last_hip_error(msg);
-    return LVLIP_EHIP;
-}
 
 int lvlip_snd_dev(const lvlip_lro_flow* f, const lvlip_snd_flow* s, uint32_t nflows, const lvlip_lro_rec* rec,
                   uint32_t n, const void* base, const lvlip_frame_desc* fd, lvlip_snd_result* res, void* stream) {
@@ -308,15 +274,15 @@ int lvlip_snd_dev(const lvlip_lro_flow* f, const lvlip_snd_flow* s, uint32_t nfl
         ((uintptr_t)res & 15u))
         return LVLIP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    int rc = snd_hip_result(hipMemsetAsync(res, 0, (size_t)nflows * sizeof *res, st), "lvlip_snd_dev: memset");
+    int rc = lvlip_launch_status(hipMemsetAsync(res, 0, (size_t)nflows * sizeof *res, st), "lvlip_snd_dev: memset");
     if (rc != LVLIP_OK) return rc;
     const uint32_t grid = (uint32_t)(((uint64_t)n + 255u) / 256u);
     hipLaunchKernelGGL(lvlip::k_snd_rec, dim3(grid), dim3(256), 0, st, f, s, nflows, rec, n, res);
-    rc = snd_hip_result(hipGetLastError(), "k_snd_rec");
+    rc = lvlip_launch_status(hipGetLastError(), "k_snd_rec");
     if (rc != LVLIP_OK) return rc;
     const uint32_t fgrid = (nflows + lvlip::SND_WAVES - 1u) / lvlip::SND_WAVES;
     hipLaunchKernelGGL(lvlip::k_snd_fin, dim3(fgrid), dim3(256), 0, st, s, nflows, (const uint8_t*)base, fd, res);
-    return snd_hip_result(hipGetLastError(), "k_snd_fin");
+    return lvlip_launch_status(hipGetLastError(), "k_snd_fin");
 }
 
 int lvlip_rtx_dev(const lvlip_lro_flow* f, const lvlip_lro_result* lro, const lvlip_snd_flow* s,
@@ -331,7 +297,7 @@ int lvlip_rtx_dev(const lvlip_lro_flow* f, const lvlip_lro_result* lro, const lv
     const uint32_t grid = (uint32_t)(((uint64_t)nslots + lvlip::RTX_SLOTS - 1u) / lvlip::RTX_SLOTS);
     hipLaunchKernelGGL(lvlip::k_rtx, dim3(grid), dim3(256), 0, (hipStream_t)stream, f, lro, s, snd, nflows, nslots,
                        (uint8_t*)base, fd, fd_out);
-    return snd_hip_result(hipGetLastError(), "k_rtx");
+    return lvlip_launch_status(hipGetLastError(), "k_rtx");
 }
 
 }  // extern "C"
