@@ -12,7 +12,15 @@ examples/snd_loop.c, and the kernels' scratch size.
 The model (model_snd, model_rtx) restates src/tcp_input.c:330-350 and :66-92
 mod 2^32 with struct.unpack on the ring's bytes; the frames a retransmit must
 leave come from lvlip_tso_cpu run with a template that carries the new ack_seq
-and window.  tests/test_snd_gpu.py shares both, with the cases."""
+and window.  tests/test_snd_gpu.py shares both, with the cases.
+
+Every frame of those cases was cut by lvlip_tso_cpu: ihl 5, hl 5, fd.len == 14
++ ip.len.  The foreign frames at the end are hand-made (TCP options, bytes
+behind the segment, addresses whose pseudo-header sum wraps, a 0x46 byte 14,
+zero-length frames, the last accepted and first refused lengths), and what a
+retransmit must leave of them (model_rtx_bytes) is stated from the ring's
+bytes and pyoracle.checksum alone, without lvlip_tso_cpu."""
+import collections
 import ctypes
 import functools
 import json
@@ -25,7 +33,8 @@ import numpy as np
 import pytest
 
 import lvlip
-from test_ack_cpu import make_flows, template_hdr
+import pyoracle
+from test_ack_cpu import ETH, make_flows, template_hdr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "snd_ref.json")
@@ -653,6 +662,357 @@ def test_pseudo_header_carry_is_lost_and_depends_on_the_payload():
     got = ring.copy()
     assert np.array_equal(lvlip.rtx_cpu(flows, None, snd, None, got, fd), want_fd)
     assert np.array_equal(got, want) and not np.array_equal(got, ring)
+
+
+# ---------------------------------------------------------- foreign frames --
+#
+# Frames no lvlip call cut: TCP options, bytes behind the segment, version/ihl
+# bytes and lengths the retransmit refuses.  What the calls must leave comes
+# from the frames' bytes and pyoracle.checksum alone (model_snd above,
+# model_rtx_bytes below): lvlip_tso_cpu, which shares tcp_hdr.h with the code
+# under test, has no part in it.  tests/test_snd_gpu.py runs the same queues
+# through the device forms.
+
+# One queue entry.  The fields sit where the calls read them (ip.len at 16,
+# seq at 38, hl in byte 46), whatever byte 14 says: ip.len = 4 ihl + 4 hl +
+# dlen - short, the frame is 14 + ip.len bytes, all bytes behind byte 53 (the
+# options, then the payload) random, then `pad` nonzero bytes that fd.len
+# counts and ip.len does not; fd.len is `cut` bytes short of all that.
+Spec = collections.namedtuple("Spec", "dlen hl ihl pad cut short", defaults=(5, 5, 0, 0, 0))
+PAD_SEED = 1  # Foreign asserts what this has to achieve: every padded frame's sum changes with its pad
+
+
+def _seed(fr: bytes, l4len: int) -> int:
+    """tcp_udp_checksum's start value (src/tcp.c:87-98): u32 adds of the
+    addresses as stored, the carry out of bit 31 lost."""
+    saddr, daddr = struct.unpack_from("<II", fr, 26)
+    return (saddr + daddr + 0x0600 + (((l4len & 0xFF) << 8) | (l4len >> 8 & 0xFF))) & M32
+
+
+def foreign_frame(rng, flow, seq: int, sp: Spec) -> bytes:
+    """The bytes of one queue entry, pad included: a right IPv4 header
+    checksum, an ack_seq, window and TCP checksum a retransmit replaces."""
+    iplen = 4 * sp.ihl + 4 * sp.hl + sp.dlen - sp.short
+    saddr, daddr = struct.pack("<I", int(flow["daddr"])), struct.pack("<I", int(flow["saddr"]))
+    ip = bytearray(struct.pack("!BBHHHBBH4s4s", 0x40 | sp.ihl, 0, iplen, 0x1234, 0x4000, 64, 6, 0, saddr, daddr))
+    ip[10:12] = struct.pack("<H", pyoracle.checksum(bytes(ip), 20, 0))
+    sport, dport = struct.unpack("<HH", struct.pack("!HH", int(flow["dport"]), int(flow["sport"])))
+    tcp = struct.pack("!HHIIBBHHH", sport, dport, seq & M32, 0xDEADBEEF, sp.hl << 4, 0x18, 0xADBD, 0xFFFF, 0)
+    tail = rng.integers(0, 256, iplen - 40, dtype=np.uint8).tobytes()
+    return ETH + bytes(ip) + tcp + tail
+
+
+class Foreign:
+    """Hand-made write queues in one canary-filled ring: queues[k] is the list
+    of Specs of flow k's queue, whose first frame starts at residue[k] mod 16
+    and every later one a residue further, at least one canary byte between
+    two frames.  The attributes are Case's, so that make_records and the
+    device tests' runners take either."""
+
+    def __init__(self, queues, residue=None, rtx=None, una=None, addr=None, seed=0, pad_seed=PAD_SEED):
+        n = len(queues)
+        rng, prng = np.random.default_rng(seed), np.random.default_rng(pad_seed)
+        self.flows = make_flows(n, addr=addr)
+        self.specs = [sp for q in queues for sp in q]
+        self.una = [(0xFFFFFC00 + 0x10203 * k) & M32 if una is None else una[k] for k in range(n)]
+        self.fd = np.zeros(len(self.specs), dtype=lvlip.FRAME_DESC_DTYPE)
+        self.snd = np.zeros(n, dtype=lvlip.SND_FLOW_DTYPE)
+        frames, off, i = [], 16, 0
+        for k, q in enumerate(queues):
+            seq = self.una[k]
+            if residue is not None and q:
+                off += (residue[k] - off) % 16
+            self.snd[k]["seg0"], self.snd[k]["nseg"] = i, len(q)
+            for sp in q:
+                fr = foreign_frame(rng, self.flows[k], seq, sp)
+                assert len(fr) == 14 + struct.unpack_from("!H", fr, 16)[0] >= 54
+                if sp.pad:
+                    fr += prng.integers(1, 256, sp.pad, dtype=np.uint8).tobytes()
+                    self._assert_pad_changes_the_sum(fr, sp)
+                frames.append((off, fr))
+                self.fd[i]["offset"], self.fd[i]["len"] = off, len(fr) - sp.cut
+                off += len(fr) + ((1 - len(fr)) % 16 or 16)
+                seq += max(sp.dlen - sp.short, 0)
+                i += 1
+            self.snd[k]["snd_una"], self.snd[k]["snd_nxt"] = self.una[k], seq & M32
+        self.ring = np.full(off + GUARD, CANARY, dtype=np.uint8)
+        for o, fr in frames:
+            self.ring[o:o + len(fr)] = np.frombuffer(fr, dtype=np.uint8)
+        self.snd["rtx"] = [len(q) + 1 for q in queues] if rtx is None else rtx  # a slot behind every queue's end
+        self.snd["win"] = (0x1234 + 257 * np.arange(n)) & 0xFFFF
+        self.nslots, self.nfd = lvlip.snd_plan(self.snd)
+        assert self.nfd == self.fd.size
+
+    @staticmethod
+    def _assert_pad_changes_the_sum(fr: bytes, sp: Spec) -> None:
+        """What makes a wrong end mask visible: summed to fd.len instead of
+        14 + ip.len, with the right length in the seed or the wrong one, the
+        field comes out different."""
+        end = len(fr) - sp.pad
+        z = bytearray(fr)
+        z[50:52] = b"\0\0"
+        right = pyoracle.checksum(bytes(z[34:end]), end - 34, _seed(fr, end - 34))
+        assert pyoracle.checksum(bytes(z[34:]), len(fr) - 34, _seed(fr, end - 34)) != right, sp
+        assert pyoracle.checksum(bytes(z[34:]), len(fr) - 34, _seed(fr, len(fr) - 34)) != right, sp
+
+    def span(self, k):
+        return (int(self.snd[k]["snd_nxt"]) - int(self.snd[k]["snd_una"])) & M32
+
+    def residues(self):
+        """{Spec: the residues mod 16 its frames start at}."""
+        r = collections.defaultdict(set)
+        for sp, d in zip(self.specs, self.fd):
+            r[sp].add(int(d["offset"]) % 16)
+        return r
+
+
+def model_rtx_bytes(q, lro_res, snd_res, ring_before: np.ndarray):
+    """(ring, fd_out) a retransmit must leave, from the header's text and the
+    ring's bytes: a live frame gets htonl(ack) at 42..45, htons(win) at 48..49
+    and, at 50..51, the oracle's checksum over [34, 14 + ip.len) with the field
+    zeroed and the seed of src/tcp.c:87-98; no other byte changes."""
+    want = ring_before.copy()
+    fd_out = np.zeros(q.nslots, dtype=lvlip.FRAME_DESC_DTYPE)
+    for k in range(q.flows.size):
+        s = q.snd[k]
+        popped = int(snd_res[k]["popped"]) if snd_res is not None else 0
+        ack = (int(q.flows[k]["rcv_nxt"]) + (int(lro_res[k]["delivered"]) if lro_res is not None else 0)) & M32
+        for j in range(int(s["rtx"])):
+            if popped + j >= int(s["nseg"]):
+                continue
+            d = q.fd[int(s["seg0"]) + popped + j]
+            o, n = int(d["offset"]), int(d["len"])
+            if n < 54:
+                continue
+            fr = bytearray(ring_before[o:o + n].tobytes())
+            iplen, hl = struct.unpack_from("!H", fr, 16)[0], fr[46] >> 4
+            if fr[14] != 0x45 or 14 + iplen > n or hl < 5 or 20 + 4 * hl > iplen:
+                continue
+            fr[42:46] = struct.pack("!I", ack)
+            fr[48:50] = struct.pack("!H", int(s["win"]))
+            fr[50:52] = b"\0\0"
+            l4len = iplen - 20
+            fr[50:52] = struct.pack("<H", pyoracle.checksum(bytes(fr[34:14 + iplen]), l4len, _seed(fr, l4len)))
+            want[o:o + n] = np.frombuffer(bytes(fr), dtype=np.uint8)
+            fd_out[int(s["slot0"]) + j] = d
+    return want, fd_out
+
+
+OPTION_HLS, OPTION_DLENS = (6, 8, 11, 15), (0, 1, 2, 3, 37)
+PADS, PAD_DLENS, PAD_HLS = (1, 2, 3, 6, 15, 16, 17, 46), (0, 1, 2), (5, 6)
+WRAP_ADDR = (bytes((254, 255, 255, 255)), bytes((7, 0, 0, 128)))
+HEAD_A = (Spec(10, hl=7, ihl=6), Spec(5, hl=15), Spec(0), Spec(3))  # snd_una 1000: end_seq 1010, 1015, 1015, 1018
+HEAD_B = (Spec(0), Spec(4))                                         # snd_una 2^32 - 2: end_seq 2^32 - 2, 2
+HEAD_UNA = (1000, 0xFFFFFFFE)
+EDGE_LIVE_HL, EDGE_DEAD_HL = Spec(0, hl=6), Spec(0, hl=7, short=4)   # 20 + 4 hl == ip.len, == ip.len + 4
+EDGE_LIVE_LEN, EDGE_DEAD_LEN = Spec(3), Spec(3, cut=1)               # 14 + ip.len == fd.len, == fd.len + 1
+
+
+@functools.lru_cache(maxsize=None)
+def foreign(name: str) -> Foreign:
+    """The foreign queues by name; every Spec of each starts at all 16
+    residues mod 16.
+    options  4, 12, 24 and 40 random option bytes (hl 6, 8, 11, 15): with the
+             frame at residue r the option region [54, 34 + 4 hl) ends inside
+             k_rtx's first sweep chunk, on a chunk edge and beyond it; 0, 1, 2,
+             3 and 37 payload bytes.
+    padding  1, 2, 3, 6 (a 54-byte frame padded to 60), 15, 16, 17 and 46 bytes
+             behind the segment, so that 14 + ip.len and fd.len fall in one
+             chunk, in adjacent ones and a whole chunk apart; 0, 1 and 2
+             payload bytes, hl 5 and 6.
+    carry    254.255.255.255 -> 7.0.0.128: the u32 pseudo-header sum wraps;
+             hl 5 and 8.
+    heads    what the ACK side meets at the head of a queue: byte 14 0x46 with
+             hl 7, hl 15, zero-length frames at the head and in mid-queue, 16
+             times over.
+    edges    the retransmit's last accepted and first refused header length
+             and fd.len, side by side."""
+    if name == "options":
+        q = Foreign([[Spec(d, hl=h)] * 16 for h in OPTION_HLS for d in OPTION_DLENS], seed=31)
+    elif name == "padding":
+        q = Foreign([[Spec(d, hl=h, pad=p)] * 16 for p in PADS for h in PAD_HLS for d in PAD_DLENS], seed=32)
+    elif name == "carry":
+        q = Foreign([[Spec(d, hl=h)] * 16 for h in (5, 8) for d in (37, 600)], addr=WRAP_ADDR, seed=33)
+        for d in q.fd:
+            saddr, daddr = struct.unpack_from("<II", q.ring[int(d["offset"]):int(d["offset"]) + 54].tobytes(), 26)
+            assert saddr + daddr >= 1 << 32
+    elif name == "heads":
+        q = Foreign([list(HEAD_A if k % 2 == 0 else HEAD_B) for k in range(32)], una=HEAD_UNA * 16,
+                    residue=[(k // 2 + (0 if k % 2 == 0 else 4)) % 16 for k in range(32)], seed=34)
+    elif name == "edges":
+        q = Foreign([[sp] * 16 for sp in (EDGE_LIVE_HL, EDGE_DEAD_HL, EDGE_LIVE_LEN, EDGE_DEAD_LEN)], seed=35)
+    else:
+        raise KeyError(name)
+    assert all(r == set(range(16)) for r in q.residues().values()), name
+    return q
+
+
+FOREIGN = ("options", "padding", "carry", "heads", "edges")
+DEAD_SPECS = {"heads": {HEAD_A[0]}, "edges": {EDGE_DEAD_HL, EDGE_DEAD_LEN}}  # entries a retransmit leaves alone
+
+
+def foreign_rtx_inputs(q: Foreign, with_results: bool):
+    """(lro results, snd results): None, None (every queue from its head, the
+    slot behind its end dead), or a random delivered and a popped of 0 .. nseg."""
+    if not with_results:
+        return None, None
+    lro, sres = rtx_inputs(q, 12)
+    sres["popped"][:3] = (0, 5, int(q.snd[2]["nseg"]))  # all live, the tail dead, all dead
+    return lro, sres
+
+
+def assert_receiver_accepts(name: str, ring: np.ndarray, fd_out: np.ndarray) -> None:
+    """The re-sent frames as a receiver sees them, pad and all: lvlip_lro_cpu
+    with LVLIP_RX_VERIFY_L4 and no flow says NO_FLOW for a frame whose
+    checksums it accepted.  Its pseudo header keeps the carries (RFC 1071), so
+    it accepts a frame exactly when the reference's seed lost none; the carry
+    queues' frames all lost one, and the receiver says so."""
+    live = fd_out[fd_out["len"] > 0]
+    assert live.size
+    _, rec = lvlip.lro_cpu(ring, live, np.zeros(0, dtype=lvlip.LRO_FLOW_DTYPE), lvlip.RX_VERIFY_L4,
+                           out=np.zeros(1, dtype=np.uint8))
+    if name == "carry":
+        assert (rec["status"] == lvlip.RX_BAD_L4).all()
+    else:
+        assert (rec["status"] == lvlip.LRO_NO_FLOW).all()
+
+
+def check_rtx_foreign(name: str, with_results: bool, run) -> None:
+    """run(q, lro, sres, ring) -> fd_out rewrites `ring` in place; both against
+    the model, byte for byte, with the preconditions that keep that from being
+    vacuous."""
+    q = foreign(name)
+    lro, sres = foreign_rtx_inputs(q, with_results)
+    want, want_fd = model_rtx_bytes(q, lro, sres, q.ring)
+    ring = q.ring.copy()
+    fd_out = run(q, lro, sres, ring)
+    assert np.array_equal(fd_out, want_fd), np.flatnonzero(fd_out != want_fd)[:5]
+    if not np.array_equal(ring, want):
+        bad = np.flatnonzero(ring != want)
+        pytest.fail(f"{name}: {bad.size} ring bytes differ, first at {int(bad[0])}: got 0x{int(ring[bad[0]]):02x}, "
+                    f"want 0x{int(want[bad[0]]):02x}")
+    dead = want_fd["len"] == 0
+    assert 0 < int(dead.sum()) < want_fd.size and (want_fd[dead]["offset"] == 0).all()
+    changed = np.flatnonzero(want != q.ring)
+    assert changed.size
+    if not with_results:  # every frame of every kind is in a slot: each is rewritten or, if it must stay, stays
+        for sp, d in zip(q.specs, q.fd):
+            o, n = int(d["offset"]), int(d["len"])
+            touched = bool(((changed >= o) & (changed < o + n + sp.cut)).any())
+            assert touched == (sp not in DEAD_SPECS.get(name, ())), sp
+    if name in ("options", "padding", "carry"):
+        assert_receiver_accepts(name, ring, fd_out)
+    if name == "carry":  # the field is not the RFC's: the lost carry shows in every frame
+        for d in want_fd[~dead]:
+            fr = bytearray(want[int(d["offset"]):int(d["offset"]) + int(d["len"])].tobytes())
+            got = bytes(fr[50:52])
+            fr[50:52] = b"\0\0"
+            s = sum(struct.unpack("<4H", bytes(fr[26:34]))) + 0x0600 + struct.unpack("<H", struct.pack("!H", len(fr) - 34))[0]
+            s = (s & 0xFFFF) + (s >> 16)
+            assert got != struct.pack("<H", pyoracle.checksum(bytes(fr[34:]), len(fr) - 34, s))
+
+
+def _rtx_cpu_in_place(q, lro, sres, ring):
+    snd_before = q.snd.copy()
+    fd_out = lvlip.rtx_cpu(q.flows, lro, q.snd, sres, ring, q.fd)
+    assert np.array_equal(q.snd, snd_before)
+    return fd_out
+
+
+@pytest.mark.parametrize("with_results", (False, True))
+@pytest.mark.parametrize("name", FOREIGN)
+def test_rtx_cpu_foreign_frames_equal_the_model(name, with_results):
+    check_rtx_foreign(name, with_results, _rtx_cpu_in_place)
+
+
+def foreign_records(q: Foreign, seed: int) -> np.ndarray:
+    """Random records of the first three flows (make_records) and, for every
+    entry in the first half of every queue, ACKs one byte before, on and one
+    byte behind its end_seq: most queues end up partly acknowledged."""
+    near = [_rec(k, frame_end_seq(q.ring, int(q.fd[int(q.snd[k]["seg0"]) + p]["offset"])) + e)
+            for k in range(q.flows.size) for p in range(int(q.snd[k]["nseg"]) // 2) for e in (-1, 0, 1)]
+    return np.concatenate([make_records(q, 100, seed, few_flows=True)] + near)
+
+
+@pytest.mark.parametrize("name", FOREIGN)
+def test_snd_cpu_foreign_frames_equal_the_model(name):
+    q = foreign(name)
+    rec = foreign_records(q, 3)
+    want = model_snd(q.flows, q.snd, rec, q.ring, q.fd)
+    got = lvlip.snd_cpu(q.flows, q.snd, rec, q.ring, q.fd)
+    assert got.tobytes() == want.tobytes(), [(k, _fields(got[k]), _fields(want[k])) for k in range(got.size)
+                                             if got[k] != want[k]][:3]
+    assert (want["popped"] > 0).any() and (want["inflight"] > 0).any() and (want["n_new"] > 0).any()
+
+
+def head_acks(q: Foreign):
+    """[(flow, ack_seq)]: for every entry of every queue, one byte before, on
+    and one byte behind its end_seq."""
+    return [(k, (frame_end_seq(q.ring, int(q.fd[int(q.snd[k]["seg0"]) + p]["offset"])) + e) & M32)
+            for k in range(q.flows.size) for p in range(int(q.snd[k]["nseg"])) for e in (-1, 0, 1)]
+
+
+def test_snd_cpu_foreign_heads_one_ack_at_a_time():
+    """Each ACK around each end_seq alone in its batch, so that `acked` is that
+    ACK's and not a later one's."""
+    q = foreign("heads")
+    popped = set()
+    for k, a in head_acks(q):
+        rec = _rec(k, a)
+        want = model_snd(q.flows, q.snd, rec, q.ring, q.fd)
+        got = lvlip.snd_cpu(q.flows, q.snd, rec, q.ring, q.fd)
+        assert got.tobytes() == want.tobytes(), (k, hex(a), _fields(got[k]), _fields(want[k]))
+        popped.add(int(want[k]["popped"]))
+    assert popped == {0, 1, 2, 3, 4}
+
+
+HEAD_NAMED = (  # (queue, ack_seq - snd_una, n_new, n_old, n_beyond, n_dup, acked, popped)
+    (0, 9, 1, 0, 0, 0, 9, 0),    # one byte before the 0x46 / hl 7 frame's end: 1000 + 62 - 24 - 28 = 1010
+    (0, 10, 1, 0, 0, 0, 10, 1),
+    (0, 11, 1, 0, 0, 0, 11, 1),
+    (0, 14, 1, 0, 0, 0, 14, 1),  # one byte before the hl 15 frame's end: 1010 + 85 - 20 - 60 = 1015
+    (0, 15, 1, 0, 0, 0, 15, 3),  # it, and the zero-length frame behind it
+    (0, 16, 1, 0, 0, 0, 16, 3),
+    (0, 17, 1, 0, 0, 0, 17, 3),
+    (0, 18, 1, 0, 0, 0, 18, 4),
+    (0, 19, 0, 0, 1, 0, 0, 0),
+    (1, -1, 0, 1, 0, 0, 0, 1),   # a zero-length head is acknowledged by snd_una itself: end_seq - snd_una == 0 <= acked
+    (1, 0, 0, 0, 0, 1, 0, 1),
+    (1, 1, 1, 0, 0, 0, 1, 1),
+    (1, 3, 1, 0, 0, 0, 3, 1),
+    (1, 4, 1, 0, 0, 0, 4, 2),    # end_seq 2: the queue wraps 2^32
+    (1, 5, 0, 0, 1, 0, 0, 1),
+)
+
+
+def head_named_check(res_of) -> None:
+    """res_of(q, rec) -> results; the literal numbers, at two of the residues."""
+    q = foreign("heads")
+    for rep in (0, 7):
+        for queue, d, n_new, n_old, n_beyond, n_dup, acked, popped in HEAD_NAMED:
+            k = 2 * rep + queue
+            una = HEAD_UNA[queue]
+            r = res_of(q, _rec(k, una + d))[k]
+            assert _fields(r) == dict(snd_una=(una + acked) & M32, acked=acked, n_new=n_new, n_dup=n_dup, n_old=n_old,
+                                      n_beyond=n_beyond, popped=popped, inflight=len((HEAD_A, HEAD_B)[queue]) - popped), \
+                (rep, queue, d)
+
+
+def test_snd_cpu_foreign_heads_named():
+    head_named_check(lambda q, rec: lvlip.snd_cpu(q.flows, q.snd, rec, q.ring, q.fd))
+
+
+def test_rtx_cpu_foreign_edges_named():
+    """20 + 4 hl == ip.len and 14 + ip.len == fd.len are live; four bytes of
+    header more, or one byte of fd.len less, and the entry stays."""
+    q = foreign("edges")
+    ring = q.ring.copy()
+    fd_out = lvlip.rtx_cpu(q.flows, None, q.snd, None, ring, q.fd)
+    live = [[bool(fd_out[int(q.snd[k]["slot0"]) + j]["len"]) for j in range(17)] for k in range(4)]
+    assert live == [[True] * 16 + [False], [False] * 17, [True] * 16 + [False], [False] * 17]
+    for k in (1, 3):
+        lo, hi = int(q.fd[16 * k]["offset"]), int(q.fd[16 * k + 15]["offset"]) + 64
+        assert np.array_equal(ring[lo:hi], q.ring[lo:hi])
 
 
 # ------------------------------------------------ the example and the kernels --

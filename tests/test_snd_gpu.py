@@ -3,8 +3,11 @@ of res, of the whole ring and of fd_out against lvlip_snd_cpu / lvlip_rtx_cpu
 on the same inputs; the whole chain lvlip_lro_dev -> lvlip_lro_advance_dev ->
 lvlip_ack_dev -> reverse lvlip_lro_dev -> lvlip_snd_dev -> lvlip_rtx_dev on one
 stream of the caller's with a single synchronise, against the CPU forms; a
-transfer with loss, run to the end through the device calls; and what the
-reference's own stack did (tests/golden/snd_ref.json).
+transfer with loss, run to the end through the device calls; what the
+reference's own stack did (tests/golden/snd_ref.json); and the foreign frames
+of tests/test_snd_cpu.py (TCP options, bytes behind the segment, a wrapping
+pseudo-header sum, the accepted and refused lengths) against the Python model
+over the ring's bytes and against the CPU forms.
 
 The record counts leave a wave partly filled, fill it, and spill one record
 into the next (63, 64, 65), and end a grid of two workgroups on one lane
@@ -19,8 +22,9 @@ import pytest
 import torch
 
 import lvlip
-from test_snd_cpu import (CANARY, GUARD, M32, Case, _rec, fixture, golden_resend, golden_ring, golden_snd, make_records,
-                          model_rtx, rtx_inputs)
+from test_snd_cpu import (CANARY, FOREIGN, GUARD, M32, Case, _rec, check_rtx_foreign, fixture, foreign, foreign_records,
+                          golden_resend, golden_ring, golden_snd, head_acks, head_named_check, make_records, model_rtx,
+                          model_snd, rtx_inputs)
 
 pytestmark = pytest.mark.gpu
 
@@ -217,6 +221,64 @@ def test_rtx_dev_leaves_frames_it_cannot_rewrite(dev):
     got, got_fd = run_rtx_dev(c, None, None, dev, ring=ring, fd=fd)
     assert np.array_equal(got_fd, want_fd)
     assert_same_ring(got, want, "frames that stay")
+
+
+# ---------------------------------------------------------- foreign frames --
+#
+# The queues of test_snd_cpu.foreign (TCP options, bytes behind the segment,
+# addresses whose pseudo-header sum wraps, a 0x46 byte 14, zero-length frames,
+# the last accepted and first refused lengths; every kind at every residue mod
+# 16) through the device forms, against the Python model over the ring's bytes
+# AND against the CPU forms.
+
+@pytest.mark.parametrize("name", FOREIGN)
+def test_snd_dev_foreign_frames_equal_model_and_cpu(name, dev):
+    q = foreign(name)
+    rec = foreign_records(q, 3)
+    want = model_snd(q.flows, q.snd, rec, q.ring, q.fd)
+    got = run_snd_dev(q, rec, dev)
+    assert_same_res(got, want, f"{name}: against the model")
+    assert_same_res(got, lvlip.snd_cpu(q.flows, q.snd, rec, q.ring, q.fd), f"{name}: against the CPU form")
+    assert (want["popped"] > 0).any() and (want["inflight"] > 0).any() and (want["n_new"] > 0).any()
+
+
+def test_snd_dev_foreign_heads_one_ack_at_a_time(dev):
+    """An ACK one byte before, on and one byte behind every end_seq of the
+    head queues, each alone in its batch (the inputs uploaded once)."""
+    q = foreign("heads")
+    n = q.flows.size
+    ins = [_t(a, dev) for a in (q.flows, q.snd, q.ring, q.fd)]
+    res_t = torch.full((32 * n + GUARD,), CANARY, dtype=torch.uint8, device=dev)
+    popped = set()
+    for k, a in head_acks(q):
+        rec = _rec(k, a)
+        lvlip.snd_dev(ins[0], ins[1], _t(rec, dev), ins[2], ins[3], res_t[:32 * n])
+        got = res_t.cpu().numpy()
+        assert (got[32 * n:] == CANARY).all(), "written behind res"
+        got = got[:32 * n].view(lvlip.SND_RESULT_DTYPE)
+        assert_same_res(got, model_snd(q.flows, q.snd, rec, q.ring, q.fd), f"flow {k}, ack {a:#x}: against the model")
+        assert_same_res(got, lvlip.snd_cpu(q.flows, q.snd, rec, q.ring, q.fd), f"flow {k}, ack {a:#x}: against the CPU form")
+        popped.add(int(got[k]["popped"]))
+    assert popped == {0, 1, 2, 3, 4}
+
+
+def test_snd_dev_foreign_heads_named(dev):
+    head_named_check(lambda q, rec: run_snd_dev(q, rec, dev))
+
+
+@pytest.mark.parametrize("with_results", (False, True))
+@pytest.mark.parametrize("name", FOREIGN)
+def test_rtx_dev_foreign_frames_equal_model_and_cpu(name, with_results, dev):
+    def run(q, lro, sres, ring):
+        cpu = ring.copy()
+        cpu_fd = lvlip.rtx_cpu(q.flows, lro, q.snd, sres, cpu, q.fd)
+        got, got_fd = run_rtx_dev(q, lro, sres, dev, ring=ring)
+        assert np.array_equal(got_fd, cpu_fd), f"{name}: fd_out against the CPU form"
+        assert_same_ring(got, cpu, f"{name}: against the CPU form")
+        ring[:] = got
+        return got_fd
+
+    check_rtx_foreign(name, with_results, run)
 
 
 # ---------------------------------------------------------------- the chain --
