@@ -14,7 +14,6 @@
 
 #define SND_HDR TCP_FRAME_HDR
 #define NONE 0xFFFFFFFFu
-#define ACK_FLAG 0x10u
 
 /* ------------------------------------------------------------------ plan -- */
 
@@ -79,12 +78,8 @@ int lvlip_snd_cpu(const lvlip_lro_flow *f, const lvlip_snd_flow *s, uint32_t nfl
     memset(res, 0, (size_t)nflows * sizeof *res);
     for (uint32_t i = 0; i < n; i++) {
         const lvlip_lro_rec *r = &rec[i];
-        const uint32_t k = r->flow;
-        if (k >= nflows) continue;
-        if (r->status != LVLIP_LRO_PLACED && r->status != LVLIP_LRO_NO_DATA && r->status != LVLIP_LRO_OUT_OF_WINDOW)
-            continue;
-        /* fifth check, src/tcp_input.c:312; first check, :106-107, on the segment's start */
-        if (!(r->tcp_flags & ACK_FLAG) || r->rel > f[k].rcv_wnd) continue;
+        const uint32_t k = rec_ack_flow(r, f, nflows);
+        if (k == NONE) continue;
         const uint32_t d = r->ack_seq - s[k].snd_una, span = s[k].snd_nxt - s[k].snd_una;
         if (d == 0) {
             res[k].n_dup++;
@@ -114,32 +109,65 @@ int lvlip_snd_cpu(const lvlip_lro_flow *f, const lvlip_snd_flow *s, uint32_t nfl
 
 /* ------------------------------------------------------------ retransmit -- */
 
+/* one slot: queue entry e of flow k (NONE: dead) rewritten in place as tcp_transmit_skb leaves it */
+static void rtx_slot(const lvlip_lro_flow *f, const lvlip_lro_result *lro, const lvlip_snd_flow *s, uint32_t k,
+                     uint32_t e, void *base, const lvlip_frame_desc *fd, lvlip_frame_desc *o)
+{
+    o->offset = 0, o->len = 0, o->reserved = 0;
+    if (e == NONE) return;
+    const lvlip_frame_desc d = fd[e];
+    uint8_t *p = (uint8_t *)base + d.offset, *ih = p + 14, *th = p + 34;
+    uint32_t iplen, hl;
+    if (!rtx_frame_ok(p, d.len, &iplen, &hl)) return;
+    /* tcp_transmit_skb, src/tcp_output.c:107,109 and :122,123 */
+    put_be32(th + 8, f[k].rcv_nxt + (lro ? lro[k].delivered : 0u));
+    th[14] = (uint8_t)(s[k].win >> 8);
+    th[15] = (uint8_t)s[k].win;
+    tcp_csum_tail(ih, th, iplen - 20u);
+    *o = d;
+}
+
+static int rtx_args(const lvlip_lro_flow *f, const lvlip_snd_flow *s, uint32_t nflows, uint32_t nslots,
+                    const void *base, const lvlip_frame_desc *fd, const lvlip_frame_desc *fd_out)
+{
+    if (!f || !s || !base || !fd || !fd_out) return LVLIP_EINVAL;
+    if (nflows == 0 || nflows > LVLIP_LRO_MAX_FLOWS || nslots > LVLIP_MAX_BATCH) return LVLIP_EINVAL;
+    if (s[nflows - 1u].slot0 > nslots || nslots - s[nflows - 1u].slot0 != s[nflows - 1u].rtx) return LVLIP_EINVAL;
+    return LVLIP_OK;
+}
+
 int lvlip_rtx_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, const lvlip_snd_flow *s,
                   const lvlip_snd_result *snd, uint32_t nflows, uint32_t nslots, void *base,
                   const lvlip_frame_desc *fd, lvlip_frame_desc *fd_out)
 {
     if (nslots == 0) return LVLIP_OK;
-    if (!f || !s || !base || !fd || !fd_out) return LVLIP_EINVAL;
-    if (nflows == 0 || nflows > LVLIP_LRO_MAX_FLOWS || nslots > LVLIP_MAX_BATCH) return LVLIP_EINVAL;
-    if (s[nflows - 1u].slot0 > nslots || nslots - s[nflows - 1u].slot0 != s[nflows - 1u].rtx) return LVLIP_EINVAL;
+    if (rtx_args(f, s, nflows, nslots, base, fd, fd_out) != LVLIP_OK) return LVLIP_EINVAL;
     for (uint32_t k = 0; k < nflows; k++) {
         const uint32_t popped = snd ? snd[k].popped : 0u;
-        const uint32_t ack = f[k].rcv_nxt + (lro ? lro[k].delivered : 0u);
         for (uint32_t j = 0; j < s[k].rtx; j++) {
-            lvlip_frame_desc *o = &fd_out[s[k].slot0 + j];
-            o->offset = 0, o->len = 0, o->reserved = 0;
-            if (popped >= s[k].nseg || j >= s[k].nseg - popped) continue;
-            const lvlip_frame_desc d = fd[s[k].seg0 + popped + j];
-            if (d.len < SND_HDR) continue;
-            uint8_t *p = (uint8_t *)base + d.offset, *ih = p + 14, *th = p + 34;
-            const uint32_t iplen = ((uint32_t)ih[2] << 8) | ih[3], hl = th[12] >> 4;
-            if (ih[0] != 0x45 || 14u + iplen > d.len || hl < 5u || 20u + 4u * hl > iplen) continue;
-            /* tcp_transmit_skb, src/tcp_output.c:107,109 and :122,123 */
-            put_be32(th + 8, ack);
-            th[14] = (uint8_t)(s[k].win >> 8);
-            th[15] = (uint8_t)s[k].win;
-            tcp_csum_tail(ih, th, iplen - 20u);
-            *o = d;
+            const int live = popped < s[k].nseg && j < s[k].nseg - popped;
+            rtx_slot(f, lro, s, k, live ? s[k].seg0 + popped + j : NONE, base, fd, &fd_out[s[k].slot0 + j]);
+        }
+    }
+    return LVLIP_OK;
+}
+
+/* the selective retransmit ("the scoreboard and the selective retransmit"): slot j is the j-th
+ * queue entry behind the popped ones whose scoreboard byte is 0 */
+int lvlip_rtx_sack_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, const lvlip_snd_flow *s,
+                       const lvlip_snd_result *snd, const uint8_t *sacked, uint32_t nflows, uint32_t nslots,
+                       void *base, const lvlip_frame_desc *fd, lvlip_frame_desc *fd_out, uint32_t *pick)
+{
+    if (nslots == 0) return LVLIP_OK;
+    if (!pick || rtx_args(f, s, nflows, nslots, base, fd, fd_out) != LVLIP_OK) return LVLIP_EINVAL;
+    for (uint32_t k = 0; k < nflows; k++) {
+        const uint32_t popped = snd ? snd[k].popped : 0u;
+        uint32_t q = popped < s[k].nseg ? popped : s[k].nseg;
+        for (uint32_t j = 0; j < s[k].rtx; j++) {
+            while (q < s[k].nseg && sacked && sacked[s[k].seg0 + q] != 0) q++;
+            const uint32_t e = q < s[k].nseg ? s[k].seg0 + q++ : NONE;
+            pick[s[k].slot0 + j] = e;
+            rtx_slot(f, lro, s, k, e, base, fd, &fd_out[s[k].slot0 + j]);
         }
     }
     return LVLIP_OK;

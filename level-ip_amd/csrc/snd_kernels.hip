@@ -26,7 +26,9 @@
 //               so a flow costs ceil((popped + 1) / 64) steps whatever its
 //               queue holds.
 //
-// lvlip_rtx_dev: ONE launch, k_rtx.
+// lvlip_rtx_dev: ONE launch, k_rtx.  lvlip_rtx_sack_dev ("the scoreboard and the
+// selective retransmit") is k_pick, which chooses each slot's queue entry
+// from the scoreboard, and then the same k_rtx from the queue entry onwards.
 //
 // Work mapping.  One DPP row (16 lanes) per slot, four slots per wave, 16 per
 // 256-thread workgroup, as k_tso and k_lro map their frames; slot g -> flow by
@@ -103,16 +105,11 @@ __global__ __launch_bounds__(256) void k_snd_rec(const lvlip_lro_flow* f, const 
     uint32_t flow = SND_NONE, cls = 4u, d = 0u;  // cls: 0 new, 1 duplicate, 2 old, 3 beyond, 4 no ACK
     if (i < n) {
         const uint4 r = load_global(reinterpret_cast<uint64_t>(rec + i));  // flow, rel, dlen | status | flags, ack_seq
-        const uint32_t status = (r.z >> 16) & 0xffu, flags = r.z >> 24;
-        const bool kind = status == LVLIP_LRO_PLACED || status == LVLIP_LRO_NO_DATA || status == LVLIP_LRO_OUT_OF_WINDOW;
-        if (r.x < nflows && kind && (flags & 0x10u)) {
-            // first check, src/tcp_input.c:106-107, on the segment's start; fifth check, :312
-            if (r.y <= f[r.x].rcv_wnd) {
-                const uint32_t una = s[r.x].snd_una, span = s[r.x].snd_nxt - una;
-                flow = r.x;
-                d = r.w - una;
-                cls = d == 0u ? 1u : d <= span ? 0u : d >= 0x80000000u ? 2u : 3u;  // :330, :338, :343
-            }
+        flow = rec_ack_flow(r, f, nflows);
+        if (flow != SND_NONE) {
+            const uint32_t una = s[flow].snd_una, span = s[flow].snd_nxt - una;
+            d = r.w - una;
+            cls = d == 0u ? 1u : d <= span ? 0u : d >= 0x80000000u ? 2u : 3u;  // :330, :338, :343
         }
     }
     uint64_t todo = __builtin_amdgcn_ballot_w64(cls < 4u);
@@ -179,10 +176,37 @@ __global__ __launch_bounds__(256) void k_snd_fin(const lvlip_snd_flow* s, uint32
 
 // ---------------------------------------------------------- the retransmit --
 
+// The selection pass of lvlip_rtx_sack_dev, one wave per flow: pick[slot0 + j]
+// is the j-th queue entry from seg0 + popped whose scoreboard byte is 0 (every
+// entry when sacked is NULL).  64 bytes a step, one per lane; a ballot of the
+// zero bytes and a popcount of the bits below the lane rank them.  The scan
+// ends once rtx entries are found, so a flow costs as many steps as it skips
+// marks; the slots left over get 0xFFFFFFFF.
+__global__ __launch_bounds__(256) void k_pick(const lvlip_snd_flow* s, const lvlip_snd_result* snd,
+                                                  const uint8_t* sacked, uint32_t nflows, uint32_t* pick) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t k64 = (uint64_t)blockIdx.x * SND_WAVES + (threadIdx.x >> 6);
+    if (k64 >= nflows) return;  // the whole wave
+    const uint32_t k = (uint32_t)k64;
+    const uint32_t seg0 = s[k].seg0, nseg = s[k].nseg, rtx = s[k].rtx;
+    uint32_t* out = pick + s[k].slot0;
+    uint32_t found = 0;
+    for (uint64_t c0 = snd ? snd[k].popped : 0u; c0 < nseg && found < rtx; c0 += 64u) {
+        const uint64_t i = c0 + lane;
+        const bool open = i < nseg && (!sacked || sacked[seg0 + (uint32_t)i] == 0);
+        const uint64_t b = __builtin_amdgcn_ballot_w64(open);
+        const uint32_t rank = found + (uint32_t)__builtin_popcountll(b & ((1ull << lane) - 1ull));
+        if (open && rank < rtx) out[rank] = seg0 + (uint32_t)i;
+        found += (uint32_t)__builtin_popcountll(b);
+    }
+    for (uint64_t j = (uint64_t)found + lane; j < rtx; j += 64u) out[j] = SND_NONE;
+}
+
+// with pick, the slot's queue entry is pick[slot] (0xFFFFFFFF: dead), as k_pick left it, not popped + j
 __global__ __launch_bounds__(256) void k_rtx(const lvlip_lro_flow* f, const lvlip_lro_result* lro,
                                              const lvlip_snd_flow* s, const lvlip_snd_result* snd, uint32_t nflows,
                                              uint32_t nslots, uint8_t* base, const lvlip_frame_desc* fd,
-                                             lvlip_frame_desc* fd_out) {
+                                             lvlip_frame_desc* fd_out, const uint32_t* pick) {
     const uint32_t tl = threadIdx.x & (RTX_ROW - 1u);
     const uint64_t g64 = (uint64_t)blockIdx.x * RTX_SLOTS + (threadIdx.x / RTX_ROW);
     const bool inside = g64 < nslots;
@@ -192,12 +216,18 @@ __global__ __launch_bounds__(256) void k_rtx(const lvlip_lro_flow* f, const lvli
     // flows that share a slot0 only the last has a slot)
     const uint32_t slo = slot_owner<&lvlip_snd_flow::slot0>(s, nflows, g);
     const lvlip_snd_flow* t = s + slo;
-    const uint32_t nseg = t->nseg, j = g - t->slot0;
-    const uint32_t popped = snd ? snd[slo].popped : 0u;
-    bool live = inside && j < t->rtx && popped < nseg && j < nseg - popped;
+    uint32_t e = SND_NONE;  // the slot's queue entry
+    if (pick) {
+        if (inside) e = pick[g];
+    } else {
+        const uint32_t nseg = t->nseg, j = g - t->slot0;
+        const uint32_t popped = snd ? snd[slo].popped : 0u;
+        if (inside && j < t->rtx && popped < nseg && j < nseg - popped) e = t->seg0 + popped + j;
+    }
+    bool live = e != SND_NONE;
 
     uint4 d = make_uint4(0u, 0u, 0u, 0u);  // the queue entry: offset lo, hi, len, reserved
-    if (live) d = load_global(reinterpret_cast<uint64_t>(fd + (t->seg0 + popped + j)));
+    if (live) d = load_global(reinterpret_cast<uint64_t>(fd + e));
     live = live && d.z >= (uint32_t)RTX_HDR;
     const uint64_t F = reinterpret_cast<uint64_t>(base) + (((uint64_t)d.y << 32) | d.x);  // the frame's first byte
     const int fo = (int)(F & 15ull);
@@ -214,9 +244,8 @@ __global__ __launch_bounds__(256) void k_rtx(const lvlip_lro_flow* f, const lvli
         const uint4 b = funnel16(c[i], c[i + 1], (uint32_t)fo);
         h[4 * i] = b.x, h[4 * i + 1] = b.y, h[4 * i + 2] = b.z, h[4 * i + 3] = b.w;
     }
-    const uint32_t iplen = bswap16u(h[4]);      // bytes 16-17
-    const uint32_t hl = (h[11] >> 20) & 0xfu;   // byte 46
-    live = live && ((h[3] >> 16) & 0xffu) == 0x45u && 14u + iplen <= d.z && hl >= 5u && 20u + 4u * hl <= iplen;
+    uint32_t iplen, hl;  // bytes 16-17, byte 46
+    live = rtx_frame_ok((h[3] >> 16) | (h[4] << 16), h[11], d.z, &iplen, &hl) && live;
     const int L = 14 + (int)iplen;              // the frame's bytes the segment ends at
     const uint32_t nch = live ? (uint32_t)(fo + L + 15) >> 4 : 0u;
     const uint32_t kb = (uint32_t)(fo + RTX_HDR) >> 4;  // the first chunk with a byte behind the header: 3 or 4
@@ -295,8 +324,29 @@ int lvlip_rtx_dev(const lvlip_lro_flow* f, const lvlip_lro_result* lro, const lv
         ((uintptr_t)fd & 15u) || ((uintptr_t)fd_out & 15u))
         return LVLIP_EINVAL;
     const uint32_t grid = (uint32_t)(((uint64_t)nslots + lvlip::RTX_SLOTS - 1u) / lvlip::RTX_SLOTS);
-    hipLaunchKernelGGL(lvlip::k_rtx, dim3(grid), dim3(256), 0, (hipStream_t)stream, f, lro, s, snd, nflows, nslots,
-                       (uint8_t*)base, fd, fd_out);
+    hipLaunchKernelGGL(lvlip::k_rtx, dim3(grid), dim3(256), 0, (hipStream_t)stream, f, lro, s, snd, nflows,
+                       nslots, (uint8_t*)base, fd, fd_out, (const uint32_t*)nullptr);
+    return lvlip_launch_status(hipGetLastError(), "k_rtx");
+}
+
+int lvlip_rtx_sack_dev(const lvlip_lro_flow* f, const lvlip_lro_result* lro, const lvlip_snd_flow* s,
+                       const lvlip_snd_result* snd, const uint8_t* sacked, uint32_t nflows, uint32_t nslots,
+                       void* base, const lvlip_frame_desc* fd, lvlip_frame_desc* fd_out, uint32_t* pick,
+                       void* stream) {
+    if (nslots == 0) return LVLIP_OK;
+    if (!f || !s || !base || !fd || !fd_out || !pick) return LVLIP_EINVAL;
+    if (nflows == 0 || nflows > LVLIP_LRO_MAX_FLOWS || nslots > LVLIP_MAX_BATCH) return LVLIP_EINVAL;
+    if (((uintptr_t)f & 7u) || ((uintptr_t)s & 7u) || ((uintptr_t)lro & 15u) || ((uintptr_t)snd & 15u) ||
+        ((uintptr_t)fd & 15u) || ((uintptr_t)fd_out & 15u) || ((uintptr_t)pick & 3u))
+        return LVLIP_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t fgrid = (nflows + lvlip::SND_WAVES - 1u) / lvlip::SND_WAVES;
+    hipLaunchKernelGGL(lvlip::k_pick, dim3(fgrid), dim3(256), 0, st, s, snd, sacked, nflows, pick);
+    const int rc = lvlip_launch_status(hipGetLastError(), "k_pick");
+    if (rc != LVLIP_OK) return rc;
+    const uint32_t grid = (uint32_t)(((uint64_t)nslots + lvlip::RTX_SLOTS - 1u) / lvlip::RTX_SLOTS);
+    hipLaunchKernelGGL(lvlip::k_rtx, dim3(grid), dim3(256), 0, st, f, lro, s, snd, nflows, nslots,
+                       (uint8_t*)base, fd, fd_out, (const uint32_t*)pick);
     return lvlip_launch_status(hipGetLastError(), "k_rtx");
 }
 

@@ -1,8 +1,9 @@
 /*
  * tcp_hdr.h — what the CPU forms of the device-resident TCP path (seg_cpu.c,
- * rcv_cpu.c, ack_cpu.c, snd_cpu.c) share: the byte helpers, the test a 54-byte
- * header template has to pass, the two checksum fields as ip_output and
- * tcp_transmit_skb leave them, and the plans' overlap check.  tcp_hdr_dev.h is
+ * rcv_cpu.c, ack_cpu.c, snd_cpu.c, sack_cpu.c) share: the byte helpers, the
+ * test a 54-byte header template has to pass, the two checksum fields as
+ * ip_output and tcp_transmit_skb leave them, the plans' overlap check, which
+ * records carry an ACK and which queue entries a retransmit can rewrite.  tcp_hdr_dev.h is
  * the same arithmetic on the device.  Not installed; static inline only, so a
  * file that uses part of it compiles without a warning.
  */
@@ -87,6 +88,28 @@ static inline int ranges_disjoint(uint64_t *r, size_t n)
     for (size_t k = 1; k < n; k++)
         if (r[2u * k - 1u] > r[2u * k]) return 0;
     return 1;
+}
+
+/* "Which records carry an ACK" (include/lvlip_skb.h): the record's flow when it
+ * counts for lvlip_snd_* and lvlip_sack_*, else 0xFFFFFFFF.  First check,
+ * src/tcp_input.c:106-107, on the segment's start; fifth check, :312. */
+static inline uint32_t rec_ack_flow(const lvlip_lro_rec *r, const lvlip_lro_flow *f, uint32_t nflows)
+{
+    if (r->flow >= nflows) return 0xFFFFFFFFu;
+    if (r->status != LVLIP_LRO_PLACED && r->status != LVLIP_LRO_NO_DATA && r->status != LVLIP_LRO_OUT_OF_WINDOW)
+        return 0xFFFFFFFFu;
+    if (!(r->tcp_flags & 0x10u) || r->rel > f[r->flow].rcv_wnd) return 0xFFFFFFFFu;
+    return r->flow;
+}
+
+/* The refusals of lvlip_rtx_*: the len bytes at p are a frame a retransmit can
+ * rewrite.  *iplen and *hl get the IP length and the TCP header's words. */
+static inline int rtx_frame_ok(const uint8_t *p, uint32_t len, uint32_t *iplen, uint32_t *hl)
+{
+    if (len < TCP_FRAME_HDR) return 0;
+    *iplen = ((uint32_t)p[16] << 8) | p[17];
+    *hl = p[46] >> 4;
+    return p[14] == 0x45 && 14u + *iplen <= len && *hl >= 5u && 20u + 4u * *hl <= *iplen;
 }
 
 #endif

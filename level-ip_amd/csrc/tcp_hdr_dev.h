@@ -99,6 +99,28 @@ __device__ __forceinline__ uint32_t load_u32_any(uint64_t a) {
     return __builtin_amdgcn_alignbyte(hi, lo, r);
 }
 
+// "Which records carry an ACK" (include/lvlip_skb.h): the flow of the record r
+// (flow, rel, dlen | status << 16 | flags << 24, ack_seq) when it counts for
+// lvlip_snd_* and lvlip_sack_*, else 0xFFFFFFFF.  First check,
+// src/tcp_input.c:106-107, on the segment's start; fifth check, :312.
+__device__ __forceinline__ uint32_t rec_ack_flow(const uint4 r, const lvlip_lro_flow* f, uint32_t nflows) {
+    const uint32_t status = (r.z >> 16) & 0xffu, flags = r.z >> 24;
+    const bool kind = status == LVLIP_LRO_PLACED || status == LVLIP_LRO_NO_DATA || status == LVLIP_LRO_OUT_OF_WINDOW;
+    if (r.x < nflows && kind && (flags & 0x10u)) {
+        if (r.y <= f[r.x].rcv_wnd) return r.x;
+    }
+    return 0xFFFFFFFFu;
+}
+
+// The refusals of lvlip_rtx_* on the dwords a (frame bytes 14-17) and b (bytes
+// 44-47) of a queue entry of len >= 54 bytes: version | ihl 0x45, the segment
+// inside the entry, hl at least 5 and inside the segment
+__device__ __forceinline__ bool rtx_frame_ok(uint32_t a, uint32_t b, uint32_t len, uint32_t* iplen, uint32_t* hl) {
+    *iplen = bswap16u(a >> 16);
+    *hl = (b >> 20) & 0xfu;
+    return (a & 0xffu) == 0x45u && 14u + *iplen <= len && *hl >= 5u && 20u + 4u * *hl <= *iplen;
+}
+
 }  // namespace lvlip
 
 // What a device call returns for the status of its launch or enqueued step

@@ -280,6 +280,21 @@ SIGNATURES = {
     "lvlip_rtx_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_void_p]),
+    # f2 on the device: the scoreboard and the selective retransmit (sack_cpu.c, sack_kernels.hip, snd_*)
+    "lvlip_sack_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
+    "lvlip_sack_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "lvlip_sack_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_size_t, ctypes.c_void_p]),
+    "lvlip_rtx_sack_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "lvlip_rtx_sack_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "lvlip_auto_kernel": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (ctypes.c_char_p, []),
@@ -991,6 +1006,159 @@ def rtx_dev(flows_t, lro_res_t, snd_t, snd_res_t, nslots: int, base_t, fd_t, fd_
                               nslots, base_t.data_ptr(), fd_t.data_ptr(), fd_out_t.data_ptr(), s.cuda_stream),
            "lvlip_rtx_dev")
     return fd_out_t[:16 * nslots]
+
+
+# struct lvlip_sack_result (include/lvlip_skb.h), 16 B
+SACK_RESULT_DTYPE = np.dtype([("n_blocks", "<u4"), ("n_valid", "<u4"), ("n_sacked", "<u4"), ("high", "<u4")])
+SACK_NO_PICK = 0xFFFFFFFF
+
+
+def sack_workspace_bytes(n: int, nflows: int) -> int:
+    """lvlip_sack_workspace_bytes: bytes of device workspace sack_dev needs
+    (0 without a device, for n == 0 and for n above 2^30 - 1)."""
+    return int(_lib.lvlip_sack_workspace_bytes(n, nflows))
+
+
+def sack_cpu(flows: np.ndarray, snd: np.ndarray, rec: np.ndarray, ack_base, ack_fdescs: np.ndarray, base,
+             fdescs: np.ndarray, sacked: np.ndarray) -> np.ndarray:
+    """lvlip_sack_cpu: marks IN PLACE in `sacked` (a writeable contiguous uint8
+    array, one byte per fd index) the queue entries that the SACK blocks of the
+    ACK frames ack_fdescs inside ack_base cover; rec their records, one per
+    frame.  Returns SACK_RESULT_DTYPE per flow (zeros when the call is a
+    no-op)."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    snd = np.ascontiguousarray(snd, dtype=SND_FLOW_DTYPE)
+    rec = np.ascontiguousarray(rec, dtype=LRO_REC_DTYPE)
+    if snd.size != flows.size:
+        raise ValueError("one send side per flow")
+    if not isinstance(sacked, np.ndarray) or sacked.dtype != np.uint8 or not sacked.flags.c_contiguous or \
+            not sacked.flags.writeable:
+        raise TypeError("sacked: a writeable contiguous uint8 array (the scoreboard is marked in place)")
+    buf, fd = _ring(base, fdescs, snd)
+    if sacked.size < fd.size:
+        raise ValueError("sacked: one byte per fd entry")
+    abuf = ack_base if isinstance(ack_base, np.ndarray) and ack_base.dtype == np.uint8 and \
+        ack_base.flags.c_contiguous else _as_u8(ack_base)
+    afd = np.ascontiguousarray(ack_fdescs, dtype=FRAME_DESC_DTYPE)
+    if afd.size != rec.size:
+        raise ValueError("one record per ACK frame")
+    if (afd["offset"] + afd["len"].astype(np.uint64) > abuf.size).any():
+        raise ValueError("an ACK frame lies past ack_base")
+    res = np.zeros(flows.size, dtype=SACK_RESULT_DTYPE)
+    keep = np.zeros(16, dtype=np.uint8)  # stands in for an empty buffer: the call wants non-NULL pointers
+    _check(_lib.lvlip_sack_cpu(flows.ctypes.data if flows.size else None, snd.ctypes.data if snd.size else None,
+                               flows.size, rec.ctypes.data if rec.size else None,
+                               abuf.ctypes.data if abuf.size else keep.ctypes.data,
+                               afd.ctypes.data if afd.size else None, rec.size,
+                               buf.ctypes.data if buf.size else keep.ctypes.data,
+                               fd.ctypes.data if fd.size else keep.ctypes.data,
+                               sacked.ctypes.data if sacked.size else keep.ctypes.data,
+                               res.ctypes.data if res.size else None), "lvlip_sack_cpu")
+    return res
+
+
+def sack_dev(flows_t, snd_t, rec_t, ack_base_t, ack_fd_t, base_t, fd_t, sacked_t, res_t=None, workspace_t=None,
+             stream=None):
+    """lvlip_sack_dev on CUDA uint8 tensors: marks sacked_t (one byte per fd
+    entry) in place.  rec_t 16 bytes per ACK frame, ack_fd_t their descriptors
+    inside ack_base_t, base_t / fd_t the TX ring.  Returns res_t, 16 bytes per
+    flow (a new tensor unless given).  workspace_t: at least
+    sack_workspace_bytes(n, nflows) bytes, 256-B aligned (allocated here unless
+    given).  Asynchronous on `stream` (default: current)."""
+    import torch
+
+    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize
+    n = rec_t.numel() * rec_t.element_size() // 16 if rec_t is not None else 0
+    if snd_t.numel() * snd_t.element_size() < SND_FLOW_DTYPE.itemsize * nflows:
+        raise ValueError("snd_t: 32 bytes per flow")
+    if n and ack_fd_t.numel() * ack_fd_t.element_size() < 16 * n:
+        raise ValueError("ack_fd_t: 16 bytes per record")
+    if res_t is None:
+        res_t = torch.zeros(SACK_RESULT_DTYPE.itemsize * max(nflows, 1), dtype=torch.uint8, device=flows_t.device)
+    elif res_t.numel() * res_t.element_size() < SACK_RESULT_DTYPE.itemsize * nflows:
+        raise ValueError("res_t: 16 bytes per flow")
+    if workspace_t is None:
+        workspace_t = torch.empty(max(sack_workspace_bytes(n, nflows), 256), dtype=torch.uint8,
+                                  device=flows_t.device)
+    s = stream or torch.cuda.current_stream(flows_t.device)
+    _check(_lib.lvlip_sack_dev(flows_t.data_ptr(), snd_t.data_ptr(), nflows, rec_t.data_ptr() if n else None,
+                               ack_base_t.data_ptr() if n else None, ack_fd_t.data_ptr() if n else None, n,
+                               base_t.data_ptr(), fd_t.data_ptr(), sacked_t.data_ptr(), res_t.data_ptr(),
+                               workspace_t.data_ptr(), workspace_t.numel() * workspace_t.element_size(),
+                               s.cuda_stream), "lvlip_sack_dev")
+    return res_t[:SACK_RESULT_DTYPE.itemsize * nflows]
+
+
+def rtx_sack_cpu(flows: np.ndarray, lro_res, snd: np.ndarray, snd_res, sacked, base: np.ndarray, fdescs: np.ndarray):
+    """lvlip_rtx_sack_cpu: rtx_cpu over the first entries of every queue whose
+    byte in `sacked` (uint8 per fd index, or None) is 0.  Rewrites `base` in
+    place.  Returns (fd_out, pick): FRAME_DESC_DTYPE and the uint32 fd index
+    per slot (SACK_NO_PICK for a dead slot)."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    snd = np.ascontiguousarray(snd, dtype=SND_FLOW_DTYPE)
+    if snd.size != flows.size:
+        raise ValueError("one send side per flow")
+    if not isinstance(base, np.ndarray) or base.dtype != np.uint8 or not base.flags.c_contiguous or \
+            not base.flags.writeable:
+        raise TypeError("base: a writeable contiguous uint8 array (the ring is rewritten in place)")
+    _, fd = _ring(base, fdescs, snd)
+    if sacked is not None:
+        sacked = np.ascontiguousarray(sacked, dtype=np.uint8)
+        if sacked.size < fd.size:
+            raise ValueError("sacked: one byte per fd entry")
+    if lro_res is not None:
+        lro_res = np.ascontiguousarray(lro_res, dtype=LRO_RESULT_DTYPE)
+    if snd_res is not None:
+        snd_res = np.ascontiguousarray(snd_res, dtype=SND_RESULT_DTYPE)
+    if any(r is not None and r.size != flows.size for r in (lro_res, snd_res)):
+        raise ValueError("one result per flow")
+    nslots = int(snd["rtx"].astype(np.uint64).sum()) if snd.size else 0
+    fd_out = np.zeros(nslots, dtype=FRAME_DESC_DTYPE)
+    pick = np.full(nslots, SACK_NO_PICK, dtype=np.uint32)
+    keep = np.zeros(16, dtype=np.uint8)
+    _check(_lib.lvlip_rtx_sack_cpu(flows.ctypes.data if flows.size else None,
+                                   lro_res.ctypes.data if lro_res is not None and lro_res.size else None,
+                                   snd.ctypes.data if snd.size else None,
+                                   snd_res.ctypes.data if snd_res is not None and snd_res.size else None,
+                                   sacked.ctypes.data if sacked is not None and sacked.size else None,
+                                   flows.size, nslots, base.ctypes.data if base.size else keep.ctypes.data,
+                                   fd.ctypes.data if fd.size else keep.ctypes.data,
+                                   fd_out.ctypes.data if fd_out.size else None,
+                                   pick.ctypes.data if pick.size else None), "lvlip_rtx_sack_cpu")
+    return fd_out, pick
+
+
+def rtx_sack_dev(flows_t, lro_res_t, snd_t, snd_res_t, sacked_t, nslots: int, base_t, fd_t, fd_out_t=None,
+                 pick_t=None, stream=None):
+    """lvlip_rtx_sack_dev on CUDA uint8 tensors: the selection pass, then
+    rtx_dev's kernel over the picked entries.  sacked_t (one byte per fd entry),
+    lro_res_t and snd_res_t may be None.  Returns (fd_out_t, pick_t): 16 and 4
+    bytes per slot (new tensors unless given).  Asynchronous on `stream`
+    (default: current)."""
+    import torch
+
+    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize
+    if snd_t.numel() * snd_t.element_size() < SND_FLOW_DTYPE.itemsize * nflows:
+        raise ValueError("snd_t: 32 bytes per flow")
+    if lro_res_t is not None and lro_res_t.numel() * lro_res_t.element_size() < LRO_RESULT_DTYPE.itemsize * nflows:
+        raise ValueError("lro_res_t: 48 bytes per flow")
+    if snd_res_t is not None and snd_res_t.numel() * snd_res_t.element_size() < SND_RESULT_DTYPE.itemsize * nflows:
+        raise ValueError("snd_res_t: 32 bytes per flow")
+    if fd_out_t is None:
+        fd_out_t = torch.empty(16 * max(nslots, 1), dtype=torch.uint8, device=base_t.device)
+    elif fd_out_t.numel() * fd_out_t.element_size() < 16 * nslots:
+        raise ValueError("fd_out_t: 16 bytes per slot")
+    if pick_t is None:
+        pick_t = torch.empty(4 * max(nslots, 1), dtype=torch.uint8, device=base_t.device)
+    elif pick_t.numel() * pick_t.element_size() < 4 * nslots:
+        raise ValueError("pick_t: 4 bytes per slot")
+    s = stream or torch.cuda.current_stream(base_t.device)
+    _check(_lib.lvlip_rtx_sack_dev(flows_t.data_ptr(), lro_res_t.data_ptr() if lro_res_t is not None else None,
+                                   snd_t.data_ptr(), snd_res_t.data_ptr() if snd_res_t is not None else None,
+                                   sacked_t.data_ptr() if sacked_t is not None else None, nflows, nslots,
+                                   base_t.data_ptr(), fd_t.data_ptr(), fd_out_t.data_ptr(), pick_t.data_ptr(),
+                                   s.cuda_stream), "lvlip_rtx_sack_dev")
+    return fd_out_t[:16 * nslots], pick_t[:4 * nslots]
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
