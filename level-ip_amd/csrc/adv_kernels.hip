@@ -4,12 +4,14 @@
 // first four islands beyond the prefix, every byte what rcv_cpu.c's
 // lvlip_lro_advance writes for the same records.  Nothing leaves the caller's
 // stream: six steps, each a completed launch before the next one reads it.
+// The keys, the sort and the workspace's pieces are interval_union.h's, which
+// the scoreboard (sack_kernels.hip) builds its unions from too.
 //
 //   k_adv_keys    one lane per record, one 16-B load: the 8-B key
-//                 flow << 32 | rel (flow 0x10000 for a record that does not
-//                 count: not PLACED, or flow >= nflows; it sorts behind every
-//                 flow) and the 2-B dlen (0 when it does not count)
-//   rocPRIM       radix_sort_pairs over the 49 key bits, the dlen as value.
+//                 flow << 32 | rel (IU_NO_KEY for a record that does not
+//                 count: not PLACED, or flow >= nflows) and the 2-B dlen (0
+//                 when it does not count)
+//   rocPRIM       radix_sort_pairs over the key bits, the dlen as value.
 //                 Stable and deterministic; equal keys may differ in dlen only,
 //                 and nothing below depends on their order (a running maximum
 //                 and a test against it: see k_adv_heads)
@@ -32,7 +34,7 @@
 //                 at H before the next head or at H[b - 1].  Twelve lanes store
 //                 the result's twelve words; a flow without a record gets zeros
 //
-// Workspace (adv_layout; every part 256-B aligned): two key arrays and two dlen
+// Workspace (adv_plan; every part 256-B aligned): two key arrays and two dlen
 // arrays (the sort's double buffers; H takes the key array the sort leaves
 // free), the tile maxima, the bitmap, rocPRIM's temporary storage.
 //
@@ -44,17 +46,15 @@
 
 #include <stdint.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
+#include "interval_union.h"
 #include "lvlip_skb.h"
-#include "tcp_hdr_dev.h"  // lvlip_launch_status
-#include "wave_search.h"
+#include "tcp_hdr_dev.h"  // lvlip_launch_status, lvlip_launched
+#include "wave_ops.h"
 
 namespace lvlip {
 
 constexpr uint32_t ADV_TILE = 256;      // sorted elements per scan tile: one per thread
 constexpr uint32_t ADV_SPINE = 64;      // lanes of the spine's one wave
-constexpr uint32_t ADV_KEY_BITS = 49;   // 17 bits of flow (0x10000: does not count) above 32 of rel
 constexpr uint32_t ADV_HEADS = 6;       // heads k_adv_emit looks for: five islands and the fifth one's end
 constexpr int ADV_ROUNDS = 4;           // bitmap words a lane of k_adv_emit has in flight
 constexpr uint64_t ADV_END_MASK = (1ull << 33) - 1u;
@@ -69,31 +69,13 @@ __device__ __forceinline__ uint64_t adv_val(uint64_t key, uint32_t len) {
 // flow << 33 | start of the interval: what the scan before an element is compared with
 __device__ __forceinline__ uint64_t adv_start(uint64_t key) { return ((key >> 32) << 33) | (key & 0xFFFFFFFFull); }
 
-__device__ __forceinline__ uint64_t wave_scan_max(uint64_t v, uint32_t lane) {
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint64_t o = __shfl_up(v, d, 64);
-        if (lane >= d) v = adv_max(v, o);
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_scan_add(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_adv_keys(const lvlip_lro_rec* rec, uint32_t n, uint32_t nflows,
                                                   uint64_t* key, uint16_t* len) {
     const uint64_t i = (uint64_t)blockIdx.x * ADV_TILE + threadIdx.x;
     if (i >= n) return;
     const uint4 r = reinterpret_cast<const uint4*>(rec)[i];  // flow, rel, dlen | status << 16 | flags << 24, ack
     const bool counts = ((r.z >> 16) & 0xffu) == LVLIP_LRO_PLACED && r.x < nflows;
-    key[i] = counts ? ((uint64_t)r.x << 32) | r.y : 0x10000ull << 32;
+    key[i] = counts ? ((uint64_t)r.x << 32) | r.y : IU_NO_KEY;
     len[i] = counts ? (uint16_t)(r.z & 0xffffu) : (uint16_t)0;
 }
 
@@ -118,7 +100,7 @@ __global__ __launch_bounds__(64) void k_adv_spine(uint64_t* agg, uint32_t ntiles
     const uint64_t t1 = t0 + per < ntiles ? t0 + per : ntiles;
     uint64_t m = 0;
     for (uint64_t t = t0; t < t1; ++t) m = adv_max(m, agg[t]);
-    const uint64_t incl = wave_scan_max(m, lane);
+    const uint64_t incl = wave_scan_max_u64(m, lane);
     const uint64_t before = __shfl_up(incl, 1, 64);
     uint64_t carry = lane == 0u ? 0ull : before;
     for (uint64_t t = t0; t < t1; ++t) {
@@ -136,7 +118,7 @@ __global__ __launch_bounds__(256) void k_adv_heads(const uint64_t* key, const ui
     const bool live = i < n;
     const uint64_t k = live ? key[i] : 0ull;
     const uint64_t v = live ? adv_val(k, len[i]) : 0ull;
-    const uint64_t in_wave = wave_scan_max(v, lane);
+    const uint64_t in_wave = wave_scan_max_u64(v, lane);
     if (lane == 63u) part[wave] = in_wave;
     __syncthreads();
     uint64_t carry = agg[blockIdx.x];
@@ -182,7 +164,7 @@ __global__ __launch_bounds__(256) void k_adv_emit(const lvlip_lro_flow* f, uint3
             uint64_t x = word[r];
             const uint32_t cnt = (uint32_t)__popcll(x);
             if (found >= ADV_HEADS || __ballot(cnt != 0u) == 0ull) continue;  // the same in every lane
-            const uint32_t upto = wave_scan_add(cnt, lane);
+            const uint32_t upto = wave_scan_add_u32(cnt, lane);
             const uint32_t base = found + upto - cnt;  // this lane's first head is head `base`
             const uint32_t bit0 = (uint32_t)(wb + 64u * (uint32_t)r + lane) << 6;
             for (uint32_t j = found; j < ADV_HEADS; ++j) {
@@ -228,34 +210,21 @@ struct adv_layout {
     size_t key[2], len[2], agg, bitmap, tmp, tmp_bytes, total;
 };
 
-static inline size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
-static hipError_t adv_sort(void* tmp, size_t& bytes, rocprim::double_buffer<uint64_t>& k,
-                           rocprim::double_buffer<uint16_t>& v, uint32_t n, hipStream_t s) {
-    return rocprim::radix_sort_pairs(tmp, bytes, k, v, n, 0u, ADV_KEY_BITS, s);
-}
-
 // false when rocPRIM's size query fails (no device)
 static bool adv_plan(uint32_t n, adv_layout& L) {
-    // the query asks the runtime for the device's architecture: once per size and thread
-    static thread_local uint32_t seen_n = 0;
-    static thread_local size_t seen_bytes = 0;
-    if (n != seen_n) {
+    const auto query = [n](size_t& bytes) {
         rocprim::double_buffer<uint64_t> k(nullptr, nullptr);
         rocprim::double_buffer<uint16_t> v(nullptr, nullptr);
-        size_t bytes = 0;
-        if (adv_sort(nullptr, bytes, k, v, n, nullptr) != hipSuccess) return false;
-        seen_n = n;
-        seen_bytes = bytes;
-    }
+        return iu_sort(nullptr, bytes, k, v, n, nullptr);
+    };
+    if (!iu_tmp_bytes(n, query, L.tmp_bytes)) return false;
     const size_t ntiles = ((size_t)n + ADV_TILE - 1u) / ADV_TILE, words = ((size_t)n + 63u) / 64u;
     size_t at = 0;
-    for (int j = 0; j < 2; ++j) { L.key[j] = at; at += up256((size_t)n * 8u); }
-    for (int j = 0; j < 2; ++j) { L.len[j] = at; at += up256((size_t)n * 2u); }
-    L.agg = at;    at += up256(ntiles * 8u);
-    L.bitmap = at; at += up256(words * 8u);
-    L.tmp = at;    at += up256(seen_bytes);
-    L.tmp_bytes = seen_bytes;
+    for (int j = 0; j < 2; ++j) L.key[j] = iu_carve(at, (size_t)n * 8u);
+    for (int j = 0; j < 2; ++j) L.len[j] = iu_carve(at, (size_t)n * 2u);
+    L.agg = iu_carve(at, ntiles * 8u);
+    L.bitmap = iu_carve(at, words * 8u);
+    L.tmp = iu_carve(at, L.tmp_bytes);
     L.total = at;
     return true;
 }
@@ -265,9 +234,7 @@ static bool adv_plan(uint32_t n, adv_layout& L) {
 extern "C" {
 
 size_t lvlip_lro_advance_workspace_bytes(uint32_t n, uint32_t /*nflows*/) {
-    if (n == 0 || n > LVLIP_MAX_BATCH) return 0;
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) return 0;
+    if (n == 0 || n > LVLIP_MAX_BATCH || !lvlip::iu_have_device()) return 0;
     lvlip::adv_layout L;
     return lvlip::adv_plan(n, L) ? L.total : 0;
 }
@@ -296,28 +263,28 @@ int lvlip_lro_advance_dev(const lvlip_lro_flow* f, uint32_t nflows, const lvlip_
     uint64_t* agg = (uint64_t*)(ws + L.agg);
     uint64_t* bitmap = (uint64_t*)(ws + L.bitmap);
     hipError_t e;
+    int rc;
 
     hipLaunchKernelGGL(k_adv_keys, dim3(ntiles), dim3(ADV_TILE), 0, s, rec, n, nflows, keys.current(),
                        lens.current());
-    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_adv_keys");
+    if ((rc = lvlip_launched("k_adv_keys")) != LVLIP_OK) return rc;
     size_t tmp_bytes = L.tmp_bytes;
-    if ((e = adv_sort(ws + L.tmp, tmp_bytes, keys, lens, n, s)) != hipSuccess)
+    if ((e = iu_sort(ws + L.tmp, tmp_bytes, keys, lens, n, s)) != hipSuccess)
         return lvlip_launch_status(e, "lvlip_lro_advance_dev: radix sort");
     const uint64_t* sorted = keys.current();
     const uint16_t* slen = lens.current();
     uint64_t* H = keys.alternate();  // the sort is done with it
     hipLaunchKernelGGL(k_adv_reduce, dim3(ntiles), dim3(ADV_TILE), 0, s, sorted, slen, n, agg);
-    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_adv_reduce");
+    if ((rc = lvlip_launched("k_adv_reduce")) != LVLIP_OK) return rc;
     hipLaunchKernelGGL(k_adv_spine, dim3(1), dim3(ADV_SPINE), 0, s, agg, ntiles);
-    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_adv_spine");
+    if ((rc = lvlip_launched("k_adv_spine")) != LVLIP_OK) return rc;
     hipLaunchKernelGGL(k_adv_heads, dim3(ntiles), dim3(ADV_TILE), 0, s, sorted, slen, n, (const uint64_t*)agg, H,
                        bitmap);
-    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_adv_heads");
+    if ((rc = lvlip_launched("k_adv_heads")) != LVLIP_OK) return rc;
     const uint32_t egrid = (uint32_t)(((uint64_t)nflows + 3u) / 4u);
     hipLaunchKernelGGL(k_adv_emit, dim3(egrid), dim3(256), 0, s, f, nflows, sorted, (const uint64_t*)H,
                        (const uint64_t*)bitmap, n, res);
-    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_adv_emit");
-    return LVLIP_OK;
+    return lvlip_launched("k_adv_emit");
 }
 
 }  // extern "C"

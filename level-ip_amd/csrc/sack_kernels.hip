@@ -6,9 +6,10 @@
 // snd_kernels.hip, beside the retransmit whose frame path they share.
 //
 // adv_kernels.hip solves the same shape of problem, a union of intervals per
-// flow, and this file follows it; here an element is a block, not a record: up
-// to 4 n elements, the key flow << 32 | l, the value the 32-bit r.  res is
-// zeroed on the stream, then:
+// flow, and both take the keys, the sort and the workspace's pieces from
+// interval_union.h; here an element is a block, not a record: up to 4 n
+// elements, the key flow << 32 | l, the value the 32-bit r.  res is zeroed on
+// the stream, then:
 //
 //   k_sack_parse  one lane per ACK record.  A record that carries an ACK
 //                 (rec_ack_flow, the predicate of k_snd_rec) has its frame's
@@ -19,17 +20,15 @@
 //                 by byte: a walk over registers would index them at run time,
 //                 which hipcc turns into scratch.  Every block goes straight to
 //                 key[4 i + b] and val[4 i + b]; an invalid or absent block
-//                 takes the key that sorts behind every flow.  n_blocks,
-//                 n_valid and high are reduced within the wave before any
-//                 atomic, flow by flow, SACK_PEEL times, as k_snd_rec does
-//   rocPRIM       radix_sort_pairs over the 49 key bits, r as value
+//                 takes IU_NO_KEY.  n_blocks, n_valid and high are reduced
+//                 within the wave before any atomic, flow by flow, SACK_PEEL
+//                 times (wave_peel), as k_snd_rec does
+//   rocPRIM       radix_sort_pairs over the key bits, r as value
 //   rocPRIM       inclusive max-scan of flow << 32 | r -> H: the largest end
-//                 so far inside the element's flow (the flow never decreases
-//                 along the sorted array, which makes a plain max segmented)
+//                 so far inside the element's flow
 //   rocPRIM       inclusive max-scan of (head ? i + 1 : 0) -> S: the island's
 //                 first element.  Element i is a head when i == 0 or H[i - 1]
-//                 is below its key: another flow, or every end so far below
-//                 its l (blocks that touch are one island)
+//                 is below its key (interval_union.h says why both work)
 //   k_sack_mark   a wave per flow and chunk of its queue (blockIdx.y strides
 //                 the queue, so a queue of many thousands of entries is spread
 //                 over 8 to SACK_Y waves, by the flow count): the flow's range
@@ -48,7 +47,7 @@
 // where order matters (equal keys differ in r, and a running maximum does not
 // depend on their order), so the bytes do not depend on the run.
 //
-// Workspace (sack_layout; every part 256-B aligned): two key arrays (H takes
+// Workspace (sack_plan; every part 256-B aligned): two key arrays (H takes
 // the one the sort leaves free), two value arrays (S takes the free one),
 // rocPRIM's temporary storage, the largest of the three calls'.
 //
@@ -63,14 +62,14 @@
 
 #include <stdint.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
+#include "interval_union.h"
 #include "lvlip_skb.h"
 #include "tcp_hdr_dev.h"
-#include "wave_search.h"
+#include "wave_ops.h"
 
 namespace lvlip {
 
@@ -78,25 +77,11 @@ constexpr uint32_t SACK_NONE = 0xFFFFFFFFu;
 constexpr uint32_t SACK_TILE = 256;            // records per workgroup of k_sack_parse: one per thread
 constexpr uint32_t SACK_OPT = 11;              // dwords of LDS per lane: 40 option bytes, and an odd stride
 constexpr int SACK_PEEL = 4;                   // flows a wave reduces before lanes go alone
-constexpr uint32_t SACK_KEY_BITS = 49;         // 17 bits of flow (0x10000: no block) above 32 of l
-constexpr uint64_t SACK_NO_KEY = 0x10000ull << 32;
 constexpr uint32_t SACK_WAVES = 4;             // waves (flows) per workgroup of k_sack_mark
 constexpr uint32_t SACK_Y = 1024;              // most chunks a queue is spread over
 constexpr uint32_t SACK_Y_MIN = 8;             // fewest: 65 536 flows still give a long queue eight waves
 constexpr uint32_t SACK_GRID = 1u << 17;       // workgroups of k_sack_mark the chunk count aims at
 constexpr uint32_t SACK_MAX_N = 0x3FFFFFFFu;   // 4 n + 1 must fit 32 bits: S holds element indices + 1
-
-__device__ __forceinline__ uint32_t wave_add_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
-    return v;
-}
 
 __device__ __forceinline__ uint32_t lds_byte(const uint32_t* o, uint32_t at) {
     return (o[at >> 2] >> (8u * (at & 3u))) & 0xffu;
@@ -154,7 +139,7 @@ __global__ __launch_bounds__(256) void k_sack_parse(const lvlip_lro_flow* f, con
                     const uint32_t l = lds_be32(o, pos + 2u + 8u * j) - una;
                     const uint32_t r = lds_be32(o, pos + 6u + 8u * j) - una;
                     const bool valid = l < r && r <= span;  // not D-SACK or stale, empty, beyond snd_nxt
-                    key[4u * i + nb] = valid ? ((uint64_t)flow << 32) | l : SACK_NO_KEY;
+                    key[4u * i + nb] = valid ? ((uint64_t)flow << 32) | l : IU_NO_KEY;
                     val[4u * i + nb] = valid ? r : 0u;
                     nv += valid ? 1u : 0u;
                     if (valid) high = max(high, r);
@@ -163,25 +148,19 @@ __global__ __launch_bounds__(256) void k_sack_parse(const lvlip_lro_flow* f, con
             pos += len;
         }
         for (uint32_t b = nb; b < 4u; ++b) {
-            key[4u * i + b] = SACK_NO_KEY;
+            key[4u * i + b] = IU_NO_KEY;
             val[4u * i + b] = 0u;
         }
     }
     // ---- n_blocks, n_valid, high: the wave's sums and maximum per flow, then three atomics
-    bool pending = nb != 0u;
-    uint64_t todo = __builtin_amdgcn_ballot_w64(pending);
-    for (int it = 0; it < SACK_PEEL && todo; ++it) {
-        const uint32_t fl = (uint32_t)__builtin_amdgcn_readlane((int)flow, __builtin_ctzll(todo));
-        const bool mine = pending && flow == fl;
+    const bool pending = wave_peel<SACK_PEEL>(nb != 0u, flow, [=](uint32_t fl, bool mine) {
         const uint32_t cb = wave_add_u32(mine ? nb : 0u), cv = wave_add_u32(mine ? nv : 0u);
         const uint32_t mx = wave_max_u32(mine ? high : 0u);
         uint32_t* w = reinterpret_cast<uint32_t*>(res + fl);  // n_blocks n_valid n_sacked high
         if (lane == 0u) atomicAdd(w, cb);
         if (lane == 1u && cv) atomicAdd(w + 1, cv);
         if (lane == 2u && mx) atomicMax(w + 3, mx);
-        todo &= ~__builtin_amdgcn_ballot_w64(mine);
-        if (mine) pending = false;
-    }
+    });
     if (pending) {
         uint32_t* w = reinterpret_cast<uint32_t*>(res + flow);
         atomicAdd(w, nb);
@@ -255,13 +234,6 @@ struct sack_layout {
     size_t key[2], val[2], tmp, tmp_bytes, total;
 };
 
-static inline size_t sack_up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
-static hipError_t sack_sort(void* tmp, size_t& bytes, rocprim::double_buffer<uint64_t>& k,
-                            rocprim::double_buffer<uint32_t>& v, uint32_t m, hipStream_t st) {
-    return rocprim::radix_sort_pairs(tmp, bytes, k, v, m, 0u, SACK_KEY_BITS, st);
-}
-
 static hipError_t sack_scan_end(void* tmp, size_t& bytes, const uint64_t* key, const uint32_t* val, uint64_t* H,
                                 uint32_t m, hipStream_t st) {
     auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u), sack_end{key, val});
@@ -276,29 +248,22 @@ static hipError_t sack_scan_head(void* tmp, size_t& bytes, const uint64_t* key, 
 
 // false when a size query of rocPRIM's fails (no device)
 static bool sack_plan(uint32_t n, sack_layout& L) {
-    // the queries ask the runtime for the device's architecture: once per size, device and thread
-    static thread_local uint32_t seen_n = 0;
-    static thread_local int seen_dev = -1;
-    static thread_local size_t seen_bytes = 0;
     const uint32_t m = 4u * n;
-    int device = -1;
-    if (hipGetDevice(&device) != hipSuccess) return false;
-    if (n != seen_n || device != seen_dev) {
+    const auto query = [m](size_t& bytes) {
         rocprim::double_buffer<uint64_t> k(nullptr, nullptr);
         rocprim::double_buffer<uint32_t> v(nullptr, nullptr);
         size_t a = 0, b = 0, c = 0;
-        if (sack_sort(nullptr, a, k, v, m, nullptr) != hipSuccess) return false;
-        if (sack_scan_end(nullptr, b, nullptr, nullptr, nullptr, m, nullptr) != hipSuccess) return false;
-        if (sack_scan_head(nullptr, c, nullptr, nullptr, nullptr, m, nullptr) != hipSuccess) return false;
-        seen_n = n;
-        seen_dev = device;
-        seen_bytes = a > b ? (a > c ? a : c) : (b > c ? b : c);
-    }
+        hipError_t e = iu_sort(nullptr, a, k, v, m, nullptr);
+        if (e == hipSuccess) e = sack_scan_end(nullptr, b, nullptr, nullptr, nullptr, m, nullptr);
+        if (e == hipSuccess) e = sack_scan_head(nullptr, c, nullptr, nullptr, nullptr, m, nullptr);
+        bytes = a > b ? (a > c ? a : c) : (b > c ? b : c);
+        return e;
+    };
+    if (!iu_tmp_bytes(m, query, L.tmp_bytes)) return false;
     size_t at = 0;
-    for (int j = 0; j < 2; ++j) { L.key[j] = at; at += sack_up256((size_t)m * 8u); }
-    for (int j = 0; j < 2; ++j) { L.val[j] = at; at += sack_up256((size_t)m * 4u); }
-    L.tmp = at; at += sack_up256(seen_bytes);
-    L.tmp_bytes = seen_bytes;
+    for (int j = 0; j < 2; ++j) L.key[j] = iu_carve(at, (size_t)m * 8u);
+    for (int j = 0; j < 2; ++j) L.val[j] = iu_carve(at, (size_t)m * 4u);
+    L.tmp = iu_carve(at, L.tmp_bytes);
     L.total = at;
     return true;
 }
@@ -308,9 +273,7 @@ static bool sack_plan(uint32_t n, sack_layout& L) {
 extern "C" {
 
 size_t lvlip_sack_workspace_bytes(uint32_t n, uint32_t /*nflows*/) {
-    if (n == 0 || n > lvlip::SACK_MAX_N) return 0;
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) return 0;
+    if (n == 0 || n > lvlip::SACK_MAX_N || !lvlip::iu_have_device()) return 0;
     lvlip::sack_layout L;
     return lvlip::sack_plan(n, L) ? L.total : 0;
 }
@@ -343,9 +306,9 @@ int lvlip_sack_dev(const lvlip_lro_flow* f, const lvlip_snd_flow* s, uint32_t nf
     const uint32_t pgrid = (uint32_t)(((uint64_t)n + SACK_TILE - 1u) / SACK_TILE);
     hipLaunchKernelGGL(k_sack_parse, dim3(pgrid), dim3(SACK_TILE), 0, st, f, s, nflows, rec, (const uint8_t*)ack_base,
                        ack_fd, n, keys.current(), vals.current(), res);
-    if ((e = hipGetLastError()) != hipSuccess) return lvlip_launch_status(e, "k_sack_parse");
+    if ((rc = lvlip_launched("k_sack_parse")) != LVLIP_OK) return rc;
     size_t tmp_bytes = L.tmp_bytes;
-    if ((e = sack_sort(ws + L.tmp, tmp_bytes, keys, vals, m, st)) != hipSuccess)
+    if ((e = iu_sort(ws + L.tmp, tmp_bytes, keys, vals, m, st)) != hipSuccess)
         return lvlip_launch_status(e, "lvlip_sack_dev: radix sort");
     const uint64_t* sorted = keys.current();
     uint64_t* H = keys.alternate();  // the sort is done with both
@@ -364,7 +327,7 @@ int lvlip_sack_dev(const lvlip_lro_flow* f, const lvlip_snd_flow* s, uint32_t nf
     y = y > SACK_Y ? SACK_Y : y < SACK_Y_MIN ? SACK_Y_MIN : y;
     hipLaunchKernelGGL(k_sack_mark, dim3(fgrid, y), dim3(256), 0, st, s, nflows, (const uint8_t*)base, fd, sorted,
                        (const uint64_t*)H, (const uint32_t*)S, m, sacked, res);
-    return lvlip_launch_status(hipGetLastError(), "k_sack_mark");
+    return lvlip_launched("k_sack_mark");
 }
 
 }  // extern "C"

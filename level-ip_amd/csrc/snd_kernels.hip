@@ -10,7 +10,8 @@
 //               first pending lane, counts that flow's lanes per class with
 //               ballots, takes the largest d with a butterfly max, and five
 //               lanes issue the flow's atomics (four class counts, one max);
-//               then the next flow, SND_PEEL times.  A batch of one flow (a
+//               then the next flow, SND_PEEL times (wave_peel, wave_ops.h,
+//               which k_sack_parse runs too).  A batch of one flow (a
 //               bulk sender's ACK stream) thus costs five atomics per wave
 //               instead of 128 on one address.  Lanes still pending after
 //               SND_PEEL rounds belong to a wave of many flows, whose
@@ -79,6 +80,7 @@
 #include "csum_dev.h"
 #include "row_copy.h"
 #include "tcp_hdr_dev.h"
+#include "wave_ops.h"
 
 namespace lvlip {
 
@@ -89,12 +91,6 @@ constexpr uint32_t RTX_ROW = 16;                 // lanes per slot
 constexpr uint32_t RTX_SLOTS = 256 / RTX_ROW;    // slots per workgroup
 constexpr int RTX_U = 6;                         // sweeps of a row in flight: an MTU frame in one round
 constexpr int RTX_HDR = TCP_FRAME_HDR;
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
-    return v;
-}
 
 // ------------------------------------------------------------ the ACK side --
 
@@ -112,24 +108,18 @@ __global__ __launch_bounds__(256) void k_snd_rec(const lvlip_lro_flow* f, const 
             cls = d == 0u ? 1u : d <= span ? 0u : d >= 0x80000000u ? 2u : 3u;  // :330, :338, :343
         }
     }
-    uint64_t todo = __builtin_amdgcn_ballot_w64(cls < 4u);
-    for (int it = 0; it < SND_PEEL && todo; ++it) {
-        const int lead = __builtin_ctzll(todo);
-        const uint32_t fl = (uint32_t)__builtin_amdgcn_readlane((int)flow, lead);
-        const bool mine = cls < 4u && flow == fl;
+    const bool pending = wave_peel<SND_PEEL>(cls < 4u, flow, [=](uint32_t fl, bool mine) {
         const uint32_t c0 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == 0u));
         const uint32_t c1 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == 1u));
         const uint32_t c2 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == 2u));
         const uint32_t c3 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == 3u));
-        const uint32_t mx = wave_max(mine && cls == 0u ? d : 0u);
+        const uint32_t mx = wave_max_u32(mine && cls == 0u ? d : 0u);
         uint32_t* w = reinterpret_cast<uint32_t*>(res + fl);  // snd_una acked n_new n_dup n_old n_beyond popped inflight
         const uint32_t cnt = lane == 0u ? c0 : lane == 1u ? c1 : lane == 2u ? c2 : c3;
         if (lane < 4u && cnt) atomicAdd(w + 2u + lane, cnt);
         if (lane == 4u && mx) atomicMax(w + 1, mx);
-        todo &= ~__builtin_amdgcn_ballot_w64(mine);
-        if (mine) cls = 4u;
-    }
-    if (cls < 4u) {
+    });
+    if (pending) {
         uint32_t* w = reinterpret_cast<uint32_t*>(res + flow);
         atomicAdd(w + 2u + cls, 1u);
         if (cls == 0u) atomicMax(w + 1, d);
@@ -292,6 +282,31 @@ __global__ __launch_bounds__(256) void k_rtx(const lvlip_lro_flow* f, const lvli
 
 }  // namespace lvlip
 
+// lvlip_rtx_dev (pick NULL: slot j of a flow is queue entry popped + j) and
+// lvlip_rtx_sack_dev (k_pick fills pick from the scoreboard first)
+static int rtx_launch(const lvlip_lro_flow* f, const lvlip_lro_result* lro, const lvlip_snd_flow* s,
+                      const lvlip_snd_result* snd, const uint8_t* sacked, uint32_t nflows, uint32_t nslots,
+                      void* base, const lvlip_frame_desc* fd, lvlip_frame_desc* fd_out, uint32_t* pick,
+                      void* stream) {
+    if (nslots == 0) return LVLIP_OK;
+    if (!f || !s || !base || !fd || !fd_out) return LVLIP_EINVAL;
+    if (nflows == 0 || nflows > LVLIP_LRO_MAX_FLOWS || nslots > LVLIP_MAX_BATCH) return LVLIP_EINVAL;
+    if (((uintptr_t)f & 7u) || ((uintptr_t)s & 7u) || ((uintptr_t)lro & 15u) || ((uintptr_t)snd & 15u) ||
+        ((uintptr_t)fd & 15u) || ((uintptr_t)fd_out & 15u) || ((uintptr_t)pick & 3u))
+        return LVLIP_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (pick) {
+        const uint32_t fgrid = (nflows + lvlip::SND_WAVES - 1u) / lvlip::SND_WAVES;
+        hipLaunchKernelGGL(lvlip::k_pick, dim3(fgrid), dim3(256), 0, st, s, snd, sacked, nflows, pick);
+        const int rc = lvlip_launched("k_pick");
+        if (rc != LVLIP_OK) return rc;
+    }
+    const uint32_t grid = (uint32_t)(((uint64_t)nslots + lvlip::RTX_SLOTS - 1u) / lvlip::RTX_SLOTS);
+    hipLaunchKernelGGL(lvlip::k_rtx, dim3(grid), dim3(256), 0, st, f, lro, s, snd, nflows, nslots, (uint8_t*)base, fd,
+                       fd_out, (const uint32_t*)pick);
+    return lvlip_launched("k_rtx");
+}
+
 extern "C" {
 
 int lvlip_snd_dev(const lvlip_lro_flow* f, const lvlip_snd_flow* s, uint32_t nflows, const lvlip_lro_rec* rec,
@@ -307,47 +322,25 @@ int lvlip_snd_dev(const lvlip_lro_flow* f, const lvlip_snd_flow* s, uint32_t nfl
     if (rc != LVLIP_OK) return rc;
     const uint32_t grid = (uint32_t)(((uint64_t)n + 255u) / 256u);
     hipLaunchKernelGGL(lvlip::k_snd_rec, dim3(grid), dim3(256), 0, st, f, s, nflows, rec, n, res);
-    rc = lvlip_launch_status(hipGetLastError(), "k_snd_rec");
+    rc = lvlip_launched("k_snd_rec");
     if (rc != LVLIP_OK) return rc;
     const uint32_t fgrid = (nflows + lvlip::SND_WAVES - 1u) / lvlip::SND_WAVES;
     hipLaunchKernelGGL(lvlip::k_snd_fin, dim3(fgrid), dim3(256), 0, st, s, nflows, (const uint8_t*)base, fd, res);
-    return lvlip_launch_status(hipGetLastError(), "k_snd_fin");
+    return lvlip_launched("k_snd_fin");
 }
 
 int lvlip_rtx_dev(const lvlip_lro_flow* f, const lvlip_lro_result* lro, const lvlip_snd_flow* s,
                   const lvlip_snd_result* snd, uint32_t nflows, uint32_t nslots, void* base,
                   const lvlip_frame_desc* fd, lvlip_frame_desc* fd_out, void* stream) {
-    if (nslots == 0) return LVLIP_OK;
-    if (!f || !s || !base || !fd || !fd_out) return LVLIP_EINVAL;
-    if (nflows == 0 || nflows > LVLIP_LRO_MAX_FLOWS || nslots > LVLIP_MAX_BATCH) return LVLIP_EINVAL;
-    if (((uintptr_t)f & 7u) || ((uintptr_t)s & 7u) || ((uintptr_t)lro & 15u) || ((uintptr_t)snd & 15u) ||
-        ((uintptr_t)fd & 15u) || ((uintptr_t)fd_out & 15u))
-        return LVLIP_EINVAL;
-    const uint32_t grid = (uint32_t)(((uint64_t)nslots + lvlip::RTX_SLOTS - 1u) / lvlip::RTX_SLOTS);
-    hipLaunchKernelGGL(lvlip::k_rtx, dim3(grid), dim3(256), 0, (hipStream_t)stream, f, lro, s, snd, nflows,
-                       nslots, (uint8_t*)base, fd, fd_out, (const uint32_t*)nullptr);
-    return lvlip_launch_status(hipGetLastError(), "k_rtx");
+    return rtx_launch(f, lro, s, snd, nullptr, nflows, nslots, base, fd, fd_out, nullptr, stream);
 }
 
 int lvlip_rtx_sack_dev(const lvlip_lro_flow* f, const lvlip_lro_result* lro, const lvlip_snd_flow* s,
                        const lvlip_snd_result* snd, const uint8_t* sacked, uint32_t nflows, uint32_t nslots,
                        void* base, const lvlip_frame_desc* fd, lvlip_frame_desc* fd_out, uint32_t* pick,
                        void* stream) {
-    if (nslots == 0) return LVLIP_OK;
-    if (!f || !s || !base || !fd || !fd_out || !pick) return LVLIP_EINVAL;
-    if (nflows == 0 || nflows > LVLIP_LRO_MAX_FLOWS || nslots > LVLIP_MAX_BATCH) return LVLIP_EINVAL;
-    if (((uintptr_t)f & 7u) || ((uintptr_t)s & 7u) || ((uintptr_t)lro & 15u) || ((uintptr_t)snd & 15u) ||
-        ((uintptr_t)fd & 15u) || ((uintptr_t)fd_out & 15u) || ((uintptr_t)pick & 3u))
-        return LVLIP_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t fgrid = (nflows + lvlip::SND_WAVES - 1u) / lvlip::SND_WAVES;
-    hipLaunchKernelGGL(lvlip::k_pick, dim3(fgrid), dim3(256), 0, st, s, snd, sacked, nflows, pick);
-    const int rc = lvlip_launch_status(hipGetLastError(), "k_pick");
-    if (rc != LVLIP_OK) return rc;
-    const uint32_t grid = (uint32_t)(((uint64_t)nslots + lvlip::RTX_SLOTS - 1u) / lvlip::RTX_SLOTS);
-    hipLaunchKernelGGL(lvlip::k_rtx, dim3(grid), dim3(256), 0, st, f, lro, s, snd, nflows, nslots,
-                       (uint8_t*)base, fd, fd_out, (const uint32_t*)pick);
-    return lvlip_launch_status(hipGetLastError(), "k_rtx");
+    if (nslots && !pick) return LVLIP_EINVAL;
+    return rtx_launch(f, lro, s, snd, sacked, nflows, nslots, base, fd, fd_out, pick, stream);
 }
 
 }  // extern "C"

@@ -127,3 +127,6 @@ __device__ __forceinline__ bool rtx_frame_ok(uint32_t a, uint32_t b, uint32_t le
 // (csum_kernels.hip, hidden): LVLIP_OK, LVLIP_ENODEV for hipErrorNoDevice, else
 // LVLIP_EHIP with "what: <HIP's text>" left for lvlip_last_hip_error().
 extern "C" int lvlip_launch_status(hipError_t e, const char* what);
+
+// the same for the kernel just launched
+static inline int lvlip_launched(const char* what) { return lvlip_launch_status(hipGetLastError(), what); }

@@ -204,21 +204,30 @@ def test_results_do_not_depend_on_the_run_or_the_order(dev):
 
 # ----------------------------------------------- the carry across the tiles --
 
-def test_carry_across_tiles_stays_inside_its_flow(dev):
-    """Flow k: [0, 60000) and 2900 intervals of 10 B every 20 B inside it: one
-    island over 12 tiles, so the running maximum must cross tiles.  Flow k + 1:
-    the same small intervals alone, each its own island: flow k's maximum must
-    not reach it."""
-    m = 2900
-    assert m > 2 * TILE and 20 * m + 10 <= 60000
+@pytest.mark.parametrize("m", [2900, 20000])
+def test_carry_across_tiles_stays_inside_its_flow(m, dev):
+    """Flow k: [0, 60000) at m = 2900, [0, 20 m + 10) at m = 20000, and m
+    intervals of 10 B every 20 B inside it: one island over 12 tiles, or over
+    79 of about 40 000 records' 157, where every lane of the spine scans three
+    tile maxima, so the running maximum must cross tiles and the spine's lanes.
+    A record's dlen has 16 bits, so the long interval is records of 60000 B
+    that touch, the last one shorter: between two of them it is the carried
+    maximum alone that keeps the 3000 small intervals below each one island.
+    Flow k + 1: the same small intervals alone, each its own island: flow k's
+    maximum must not reach it."""
+    long = max(60000, 20 * m + 10)
+    assert m > 2 * TILE and 20 * m + 10 <= long < 1 << 20
+    assert (m == 2900) == (2 * m + 1 <= TILE * SPINE)
+    cover = [_rec(0, c, min(60000, long - c)) for c in range(0, long, 60000)]
+    assert len(cover) == (1 if m == 2900 else 7)
     flows = plan_flows(3, 1 << 20, 0)
-    rows = [_rec(0, 0, 60000)] + [_rec(0, 20 * j, 10) for j in range(m)] + [_rec(1, 20 * j, 10) for j in range(m)]
+    rows = cover + [_rec(0, 20 * j, 10) for j in range(m)] + [_rec(1, 20 * j, 10) for j in range(m)]
     rec = np.array(rows, dtype=lvlip.LRO_REC_DTYPE)[np.random.default_rng(3).permutation(len(rows))]
     rec = np.ascontiguousarray(rec)
     got = advance_dev(flows, rec, dev)
     assert_same_results(got, flows, rec, "carry")
     nxt = int(flows[1]["rcv_nxt"])
-    assert result_tuples(got) == [(60000, m + 1, []),
+    assert result_tuples(got) == [(long, m + len(cover), []),
                                   (10, m, [((nxt + 20 * j) & 0xFFFFFFFF, (nxt + 20 * j + 10) & 0xFFFFFFFF)
                                            for j in range(1, 5)]), (0, 0, [])]
     assert int(got[0]["nsack"]) == 0 and int(got[1]["nsack"]) == 4
