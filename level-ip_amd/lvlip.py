@@ -172,135 +172,86 @@ _lib = _load(LIB_PATH)
 BUILD_ID = _stamp(_lib, LIB_PATH, "lvlip_build_id", BUILD_SOURCES)
 
 # every entry point declared in include/lvlip_csum.h, with its ctypes signature
+_P, _STR, _INT, _SZ = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_size_t
+_U8, _U16, _U32, _U64, _I32 = ctypes.c_uint8, ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int32
+_PP, _PU32, _PU64 = ctypes.POINTER(_P), ctypes.POINTER(_U32), ctypes.POINTER(_U64)
 SIGNATURES = {
-    "sum_every_16bits": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_int]),
-    "checksum": (ctypes.c_uint16, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
-    "lvlip_pseudo_sum": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
-                                            ctypes.c_uint16]),
-    "tcp_udp_checksum": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
-                                        ctypes.c_void_p, ctypes.c_uint16]),
-    "tcp_v4_checksum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
-    "ip_send_check": (None, [ctypes.c_void_p]),
-    "lvlip_csum_batch_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                            ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_csum_batch_dev_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                               ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.POINTER(LaunchCfg)]),
-    "lvlip_csum_ctx_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
-                                             ctypes.c_size_t]),
-    "lvlip_csum_ctx_destroy": (ctypes.c_int, [ctypes.c_void_p]),
-    "lvlip_csum_batch_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Iov), ctypes.c_uint32,
-                                             ctypes.c_void_p]),
-    "lvlip_csum_batch_host_flat": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                                  ctypes.c_void_p, ctypes.c_uint32,
-                                                  ctypes.c_void_p]),
-    "lvlip_csum_register": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                           ctypes.c_uint32]),
-    "lvlip_csum_unregister": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_strerror": (ctypes.c_char_p, [ctypes.c_int]),
+    "sum_every_16bits": (_U32, [_P, _INT]),
+    "checksum": (_U16, [_P, _INT, _INT]),
+    "lvlip_pseudo_sum": (_U32, [_U32, _U32, _U8, _U16]),
+    "tcp_udp_checksum": (_INT, [_U32, _U32, _U8, _P, _U16]),
+    "tcp_v4_checksum": (_INT, [_P, _U32, _U32]),
+    "ip_send_check": (None, [_P]),
+    "lvlip_csum_batch_dev": (_INT, [_P, _P, _U32, _P, _P]),
+    "lvlip_csum_batch_dev_ex": (_INT, [_P, _P, _U32, _P, _P, ctypes.POINTER(LaunchCfg)]),
+    "lvlip_csum_ctx_create": (_INT, [_PP, _INT, _SZ]),
+    "lvlip_csum_ctx_destroy": (_INT, [_P]),
+    "lvlip_csum_batch_host": (_INT, [_P, ctypes.POINTER(Iov), _U32, _P]),
+    "lvlip_csum_batch_host_flat": (_INT, [_P, _P, _SZ, _P, _U32, _P]),
+    "lvlip_csum_register": (_INT, [_P, _P, _SZ, _U32]),
+    "lvlip_csum_unregister": (_INT, [_P, _P]),
+    "lvlip_strerror": (_STR, [_INT]),
     # include/lvlip_skb.h (f1/f2 frame batches)
-    "lvlip_rx_verify": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Frame), ctypes.c_uint32,
-                                       ctypes.c_uint32, ctypes.c_void_p]),
-    "lvlip_rx_plan": (ctypes.c_uint32, [ctypes.POINTER(Frame), ctypes.c_uint32, ctypes.c_uint32,
-                                        ctypes.c_void_p, ctypes.POINTER(Iov), ctypes.c_void_p]),
-    "lvlip_rx_apply": (None, [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                              ctypes.c_void_p]),
-    "lvlip_tx_checksum": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Frame), ctypes.c_uint32]),
-    "lvlip_tx_plan": (ctypes.c_uint32, [ctypes.POINTER(Frame), ctypes.c_uint32, ctypes.POINTER(Iov),
-                                        ctypes.c_void_p]),
-    "lvlip_tx_apply": (None, [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_icmp_echo_reply_csum": (ctypes.c_uint32, [ctypes.c_uint16]),
-    "lvlip_icmp_echo_reply_fill": (ctypes.c_uint32, [ctypes.POINTER(Frame), ctypes.c_uint32]),
-    "lvlip_frames_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint32]),
-    "lvlip_rx_verify_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_void_p]),
-    "lvlip_tx_checksum_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_pseudo_sum_rfc": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
-                                               ctypes.c_uint16]),
-    "lvlip_icmp_echo_reply_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                 ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_icmp_echo_reply_dev_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                    ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "lvlip_rx_verify": (_INT, [_P, ctypes.POINTER(Frame), _U32, _U32, _P]),
+    "lvlip_rx_plan": (_U32, [ctypes.POINTER(Frame), _U32, _U32, _P, ctypes.POINTER(Iov), _P]),
+    "lvlip_rx_apply": (None, [_U32, _P, _U32, _P, _P]),
+    "lvlip_tx_checksum": (_INT, [_P, ctypes.POINTER(Frame), _U32]),
+    "lvlip_tx_plan": (_U32, [ctypes.POINTER(Frame), _U32, ctypes.POINTER(Iov), _P]),
+    "lvlip_tx_apply": (None, [_U32, _P, _P]),
+    "lvlip_icmp_echo_reply_csum": (_U32, [_U16]),
+    "lvlip_icmp_echo_reply_fill": (_U32, [ctypes.POINTER(Frame), _U32]),
+    "lvlip_frames_workspace_bytes": (_SZ, [_U32]),
+    "lvlip_rx_verify_dev": (_INT, [_P, _P, _U32, _U32, _P, _P, _P]),
+    "lvlip_tx_checksum_dev": (_INT, [_P, _P, _U32, _P, _P, _P]),
+    "lvlip_pseudo_sum_rfc": (_U32, [_U32, _U32, _U8, _U16]),
+    "lvlip_icmp_echo_reply_dev": (_INT, [_P, _P, _U32, _P, _P]),
+    "lvlip_icmp_echo_reply_dev_ex": (_INT, [_P, _P, _U32, _U32, _P, _P]),
     # Group 4: one batch over several GPUs
-    "lvlip_partition_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
-                                             ctypes.c_void_p]),
-    "lvlip_csum_batch_host_flat_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                                        ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32,
-                                                        ctypes.c_void_p]),
-    "lvlip_rx_verify_skb_list": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                ctypes.c_void_p, ctypes.c_uint32]),
-    "lvlip_tx_checksum_skb_list": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "lvlip_partition_bytes": (_INT, [_P, _U32, _U32, _P]),
+    "lvlip_csum_batch_host_flat_multi": (_INT, [_P, _U32, _P, _SZ, _P, _U32, _P]),
+    "lvlip_rx_verify_skb_list": (_INT, [_P, _P, _U32, _P, _U32]),
+    "lvlip_tx_checksum_skb_list": (_INT, [_P, _P]),
     # round 6: size-based dispatch, counters, context-free CPU frame calls
-    "lvlip_csum_ctx_set_cpu_max": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
-    "lvlip_csum_ctx_cpu_max": (ctypes.c_uint32, [ctypes.c_void_p]),
-    "lvlip_csum_ctx_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CtxStats)]),
-    "lvlip_rx_verify_cpu": (ctypes.c_int, [ctypes.POINTER(Frame), ctypes.c_uint32, ctypes.c_uint32,
-                                           ctypes.c_void_p]),
-    "lvlip_tx_checksum_cpu": (ctypes.c_int, [ctypes.POINTER(Frame), ctypes.c_uint32]),
-    "lvlip_rx_verify_skb_list_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                                    ctypes.c_uint32]),
-    "lvlip_tx_checksum_skb_list_cpu": (ctypes.c_int, [ctypes.c_void_p]),
+    "lvlip_csum_ctx_set_cpu_max": (_INT, [_P, _U32]),
+    "lvlip_csum_ctx_cpu_max": (_U32, [_P]),
+    "lvlip_csum_ctx_stats": (_INT, [_P, ctypes.POINTER(CtxStats)]),
+    "lvlip_rx_verify_cpu": (_INT, [ctypes.POINTER(Frame), _U32, _U32, _P]),
+    "lvlip_tx_checksum_cpu": (_INT, [ctypes.POINTER(Frame), _U32]),
+    "lvlip_rx_verify_skb_list_cpu": (_INT, [_P, _U32, _P, _U32]),
+    "lvlip_tx_checksum_skb_list_cpu": (_INT, [_P]),
     # f2 on the device: segmentation (seg_cpu.c, seg_kernels.hip)
-    "lvlip_tso_plan": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),
-    "lvlip_tso_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                     ctypes.c_void_p]),
-    "lvlip_tso_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "lvlip_tso_plan": (_U32, [_P, _U32, _PU64]),
+    "lvlip_tso_cpu": (_INT, [_P, _P, _U32, _P, _P]),
+    "lvlip_tso_dev": (_INT, [_P, _P, _U32, _U32, _P, _P, _P]),
     # f1 on the device: receive coalescing (rcv_cpu.c, rcv_kernels.hip)
-    "lvlip_lro_plan": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),
-    "lvlip_lro_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_lro_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_void_p]),
-    "lvlip_lro_advance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
-                                         ctypes.c_void_p]),
-    "lvlip_lro_advance_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
-    "lvlip_lro_advance_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "lvlip_lro_plan": (_U32, [_P, _U32, _PU64]),
+    "lvlip_lro_cpu": (_INT, [_P, _P, _U32, _P, _U32, _U32, _P, _P]),
+    "lvlip_lro_dev": (_INT, [_P, _P, _U32, _P, _U32, _U32, _P, _P, _P]),
+    "lvlip_lro_advance": (_INT, [_P, _U32, _P, _U32, _P]),
+    "lvlip_lro_advance_workspace_bytes": (_SZ, [_U32, _U32]),
+    "lvlip_lro_advance_dev": (_INT, [_P, _U32, _P, _U32, _P, _P, _SZ, _P]),
     # f1 on the device: the acknowledgement (ack_cpu.c, ack_kernels.hip)
-    "lvlip_ack_plan": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                         ctypes.POINTER(ctypes.c_uint64)]),
-    "lvlip_ack_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_ack_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "lvlip_ack_plan": (_U32, [_P, _P, _U32, _PU64]),
+    "lvlip_ack_cpu": (_INT, [_P, _P, _P, _U32, _U32, _P, _P]),
+    "lvlip_ack_dev": (_INT, [_P, _P, _P, _U32, _U32, _P, _P, _P]),
     # f2 on the device: the ACK side and the retransmit (snd_cpu.c, snd_kernels.hip)
-    "lvlip_snd_plan": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
-    "lvlip_snd_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_snd_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_void_p]),
-    "lvlip_rtx_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_void_p]),
-    "lvlip_rtx_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_void_p]),
+    "lvlip_snd_plan": (_U32, [_P, _U32, _PU32]),
+    "lvlip_snd_cpu": (_INT, [_P, _P, _U32, _P, _U32, _P, _P, _P]),
+    "lvlip_snd_dev": (_INT, [_P, _P, _U32, _P, _U32, _P, _P, _P, _P]),
+    "lvlip_rtx_cpu": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P]),
+    "lvlip_rtx_dev": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P]),
     # f2 on the device: the scoreboard and the selective retransmit (sack_cpu.c, sack_kernels.hip, snd_*)
-    "lvlip_sack_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
-    "lvlip_sack_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_sack_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_size_t, ctypes.c_void_p]),
-    "lvlip_rtx_sack_cpu": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_rtx_sack_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "lvlip_auto_kernel": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
-    "lvlip_batch_launches": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.POINTER(LaunchCfg)]),
-    "lvlip_build_id": (ctypes.c_char_p, []),
-    "lvlip_abi_version": (ctypes.c_int, []),
-    "lvlip_device_count": (ctypes.c_int, []),
-    "lvlip_last_hip_error": (ctypes.c_char_p, []),
+    "lvlip_sack_workspace_bytes": (_SZ, [_U32, _U32]),
+    "lvlip_sack_cpu": (_INT, [_P, _P, _U32, _P, _P, _P, _U32, _P, _P, _P, _P]),
+    "lvlip_sack_dev": (_INT, [_P, _P, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _SZ, _P]),
+    "lvlip_rtx_sack_cpu": (_INT, [_P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P]),
+    "lvlip_rtx_sack_dev": (_INT, [_P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P]),
+    "lvlip_auto_kernel": (_INT, [_I32, _U32, ctypes.POINTER(LaunchCfg)]),
+    "lvlip_batch_launches": (_U32, [_U32, ctypes.POINTER(LaunchCfg)]),
+    "lvlip_build_id": (_STR, []),
+    "lvlip_abi_version": (_INT, []),
+    "lvlip_device_count": (_INT, []),
+    "lvlip_last_hip_error": (_STR, []),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(_lib, _name)
@@ -321,6 +272,91 @@ def _as_u8(buf) -> np.ndarray:
     if isinstance(buf, np.ndarray):
         return np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
     return np.frombuffer(bytes(buf), dtype=np.uint8)
+
+
+# What the f1/f2 wrappers (tso_* .. rtx_sack_*) share.  numpy side first.
+
+_STAND_IN = np.zeros(16, dtype=np.uint8)  # for an empty buffer where a call wants a non-NULL pointer
+
+
+def _aptr(a, stand_in: bool = False):
+    """The address of an array's data; NULL (or the stand-in's) for None and
+    for an empty array."""
+    if a is not None and a.size:
+        return a.ctypes.data
+    return _STAND_IN.ctypes.data if stand_in else None
+
+
+def _is_u8(a, writeable: bool = False) -> bool:
+    """A contiguous (and writeable) uint8 array."""
+    return isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags.c_contiguous and \
+        (a.flags.writeable or not writeable)
+
+
+def _u8_inplace(buf) -> np.ndarray:
+    """_as_u8 that never copies a contiguous uint8 array."""
+    return buf if _is_u8(buf) else _as_u8(buf)
+
+
+def _planned(a: np.ndarray, dtype, what: str, writeable: bool = True) -> None:
+    """The array a *_plan call reads (and writes) in place."""
+    if a.dtype != dtype or not a.flags.c_contiguous or not (a.flags.writeable or not writeable):
+        raise TypeError(what)
+
+
+def _plan_ok(n: int, refused: str) -> int:
+    if n == PLAN_MALFORMED:
+        raise ValueError(refused)
+    return n
+
+
+def _out_u8(out, need: int) -> np.ndarray:
+    """The caller's frame or stream buffer, checked, or a new zeroed one."""
+    if out is None:
+        out = np.zeros(need, dtype=np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < need:
+        raise ValueError("out: a contiguous uint8 array of at least the plan's out_bytes")
+    return out
+
+
+# The torch side: sizes in bytes, whatever the tensor's dtype.
+
+def _nbytes(t) -> int:
+    return t.numel() * t.element_size()
+
+
+def _records(t, itemsize: int) -> int:
+    """Whole records of itemsize bytes in a tensor; 0 for None."""
+    return t.numel() * t.element_size() // itemsize if t is not None else 0
+
+
+def _need(t, name: str, per: int, n: int, unit: str, optional: bool = False) -> None:
+    if not (optional and t is None) and t.numel() * t.element_size() < per * n:
+        raise ValueError(f"{name}: {per} bytes per {unit}")
+
+
+def _tptr(t, n: int = 1):
+    """A tensor's address; NULL for None and for a batch of n == 0."""
+    return t.data_ptr() if n and t is not None else None
+
+
+def _result(t, name: str, per: int, n: int, unit: str, device, zeroed: bool = False):
+    """The caller's result tensor, checked, or a new one of per bytes for
+    each of max(n, 1); the wrapper returns its first per * n bytes."""
+    if t is None:
+        import torch
+
+        return (torch.zeros if zeroed else torch.empty)(per * max(n, 1), dtype=torch.uint8, device=device)
+    _need(t, name, per, n, unit)
+    return t
+
+
+def _stream(stream, device):
+    if stream:
+        return stream
+    import torch
+
+    return torch.cuda.current_stream(device)
 
 
 # --------------------------------------------------------------- per call --
@@ -558,7 +594,7 @@ def rx_verify_dev(base, fdescs, flags: int = 0, stream=None):
 
     n, fd = _frames_dev(base, fdescs)
     verdict = torch.empty(max(n, 1), dtype=torch.uint8, device=base.device)
-    s = stream or torch.cuda.current_stream(base.device)
+    s = _stream(stream, base.device)
     _check(_lib.lvlip_rx_verify_dev(base.data_ptr(), fd.data_ptr(), n, flags, verdict.data_ptr(),
                                     None, s.cuda_stream), "lvlip_rx_verify_dev")
     return verdict[:n]
@@ -571,7 +607,7 @@ def tx_checksum_dev(base, fdescs, stream=None):
 
     n, fd = _frames_dev(base, fdescs)
     status = torch.empty(max(n, 1), dtype=torch.uint8, device=base.device)
-    s = stream or torch.cuda.current_stream(base.device)
+    s = _stream(stream, base.device)
     _check(_lib.lvlip_tx_checksum_dev(base.data_ptr(), fd.data_ptr(), n, status.data_ptr(),
                                       None, s.cuda_stream), "lvlip_tx_checksum_dev")
     return status[:n]
@@ -587,7 +623,7 @@ def icmp_echo_reply_dev(base, fdescs, stream=None, flags: int = 0):
 
     n, fd = _frames_dev(base, fdescs)
     status = torch.empty(max(n, 1), dtype=torch.uint8, device=base.device)
-    s = stream or torch.cuda.current_stream(base.device)
+    s = _stream(stream, base.device)
     if flags == 0:
         rc = _lib.lvlip_icmp_echo_reply_dev(base.data_ptr(), fd.data_ptr(), n, status.data_ptr(), s.cuda_stream)
     else:
@@ -620,13 +656,10 @@ def tso_plan(sends: np.ndarray):
     """lvlip_tso_plan: validates the sends and fills their seg0 in place.
     Returns (nseg, out_bytes); ValueError for a malformed send or too many
     segments."""
-    if sends.dtype != TsoSend or not sends.flags.c_contiguous or not sends.flags.writeable:
-        raise TypeError("sends: a writeable contiguous TsoSend array")
+    _planned(sends, TsoSend, "sends: a writeable contiguous TsoSend array")
     out_bytes = ctypes.c_uint64(0)
-    nseg = int(_lib.lvlip_tso_plan(sends.ctypes.data if sends.size else None, sends.size,
-                                   ctypes.byref(out_bytes)))
-    if nseg == PLAN_MALFORMED:
-        raise ValueError("malformed send (or more than LVLIP_MAX_BATCH segments)")
+    nseg = _plan_ok(int(_lib.lvlip_tso_plan(_aptr(sends), sends.size, ctypes.byref(out_bytes))),
+                    "malformed send (or more than LVLIP_MAX_BATCH segments)")
     return nseg, int(out_bytes.value)
 
 
@@ -639,10 +672,7 @@ def tso_cpu(payload, sends: np.ndarray, out: Optional[np.ndarray] = None):
     pay = _as_u8(payload)
     if any(int(s["payload_off"]) + int(s["len"]) > pay.size for s in sends):
         raise ValueError("a send reads past the payload")
-    if out is None:
-        out = np.zeros(out_bytes, dtype=np.uint8)
-    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < out_bytes:
-        raise ValueError("out: a contiguous uint8 array of at least the plan's out_bytes")
+    out = _out_u8(out, out_bytes)
     fd = np.zeros(nseg, dtype=FRAME_DESC_DTYPE)
     _check(_lib.lvlip_tso_cpu(pay.ctypes.data, sends.ctypes.data, sends.size, out.ctypes.data,
                               fd.ctypes.data), "lvlip_tso_cpu")
@@ -654,14 +684,11 @@ def tso_dev(payload_t, sends_t, nseg: int, out_t, fd_t=None, stream=None):
     planned TsoSend records' bytes (96 each), out_t the frame buffer (at least
     the plan's out_bytes), fd_t (optional) 16 bytes per segment for the frame
     descriptors.  One launch on `stream` (default: current), asynchronous."""
-    import torch
-
-    n = sends_t.numel() * sends_t.element_size() // TsoSend.itemsize
-    s = stream or torch.cuda.current_stream(out_t.device)
-    if fd_t is not None and fd_t.numel() * fd_t.element_size() < 16 * nseg:
-        raise ValueError("fd_t: 16 bytes per segment")
-    _check(_lib.lvlip_tso_dev(payload_t.data_ptr(), sends_t.data_ptr(), n, nseg, out_t.data_ptr(),
-                              fd_t.data_ptr() if fd_t is not None else None, s.cuda_stream), "lvlip_tso_dev")
+    n = _records(sends_t, TsoSend.itemsize)
+    s = _stream(stream, out_t.device)
+    _need(fd_t, "fd_t", 16, nseg, "segment", optional=True)
+    _check(_lib.lvlip_tso_dev(payload_t.data_ptr(), sends_t.data_ptr(), n, nseg, out_t.data_ptr(), _tptr(fd_t),
+                              s.cuda_stream), "lvlip_tso_dev")
 
 
 # ------------------------------------- f1 on the device: receive coalescing --
@@ -696,12 +723,10 @@ def lro_flow(saddr: bytes, daddr: bytes, sport: int, dport: int, rcv_nxt: int, r
 def lro_plan(flows: np.ndarray):
     """lvlip_lro_plan: validates the flows and sorts them in place by key.
     Returns out_bytes; ValueError for a refused plan."""
-    if flows.dtype != LRO_FLOW_DTYPE or not flows.flags.c_contiguous or not flows.flags.writeable:
-        raise TypeError("flows: a writeable contiguous LRO_FLOW_DTYPE array")
+    _planned(flows, LRO_FLOW_DTYPE, "flows: a writeable contiguous LRO_FLOW_DTYPE array")
     out_bytes = ctypes.c_uint64(0)
-    n = int(_lib.lvlip_lro_plan(flows.ctypes.data if flows.size else None, flows.size, ctypes.byref(out_bytes)))
-    if n == PLAN_MALFORMED:
-        raise ValueError("refused flows (duplicate key, window, reserved bytes, overlapping ranges, too many)")
+    _plan_ok(int(_lib.lvlip_lro_plan(_aptr(flows), flows.size, ctypes.byref(out_bytes))),
+             "refused flows (duplicate key, window, reserved bytes, overlapping ranges, too many)")
     return int(out_bytes.value)
 
 
@@ -716,13 +741,10 @@ def lro_cpu(base, fdescs: np.ndarray, flows: np.ndarray, flags: int = 0, out: Op
     if any(int(d["offset"]) + int(d["len"]) > buf.size for d in fd):
         raise ValueError("a frame lies past the buffer")
     need = max((int(f["out_off"]) + int(f["rcv_wnd"]) for f in flows), default=0)
-    if out is None:
-        out = np.zeros(need, dtype=np.uint8)
-    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < need:
-        raise ValueError("out: a contiguous uint8 array of at least the plan's out_bytes")
+    out = _out_u8(out, need)
     rec = np.zeros(fd.size, dtype=LRO_REC_DTYPE)
-    _check(_lib.lvlip_lro_cpu(buf.ctypes.data, fd.ctypes.data, fd.size, flows.ctypes.data if flows.size else None,
-                              flows.size, flags, out.ctypes.data, rec.ctypes.data), "lvlip_lro_cpu")
+    _check(_lib.lvlip_lro_cpu(buf.ctypes.data, fd.ctypes.data, fd.size, _aptr(flows), flows.size, flags,
+                              out.ctypes.data, rec.ctypes.data), "lvlip_lro_cpu")
     return out, rec
 
 
@@ -732,17 +754,12 @@ def lro_dev(base_t, fd_t, flows_t, flags: int, out_t, rec_t=None, stream=None):
     be empty), out_t the stream buffer.  Returns rec_t (16 bytes per frame, a
     new tensor unless given).  One launch on `stream` (default: current),
     asynchronous."""
-    import torch
-
-    n = fd_t.numel() * fd_t.element_size() // 16
-    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize if flows_t is not None else 0
-    if rec_t is None:
-        rec_t = torch.empty(16 * max(n, 1), dtype=torch.uint8, device=out_t.device)
-    elif rec_t.numel() * rec_t.element_size() < 16 * n:
-        raise ValueError("rec_t: 16 bytes per frame")
-    s = stream or torch.cuda.current_stream(out_t.device)
-    _check(_lib.lvlip_lro_dev(base_t.data_ptr(), fd_t.data_ptr(), n, flows_t.data_ptr() if nflows else None, nflows,
-                              flags, out_t.data_ptr(), rec_t.data_ptr(), s.cuda_stream), "lvlip_lro_dev")
+    n = _records(fd_t, 16)
+    nflows = _records(flows_t, LRO_FLOW_DTYPE.itemsize)
+    rec_t = _result(rec_t, "rec_t", 16, n, "frame", out_t.device)
+    s = _stream(stream, out_t.device)
+    _check(_lib.lvlip_lro_dev(base_t.data_ptr(), fd_t.data_ptr(), n, _tptr(flows_t, nflows), nflows, flags,
+                              out_t.data_ptr(), rec_t.data_ptr(), s.cuda_stream), "lvlip_lro_dev")
     return rec_t
 
 
@@ -752,9 +769,7 @@ def lro_advance(flows: np.ndarray, rec: np.ndarray) -> np.ndarray:
     flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
     rec = np.ascontiguousarray(rec, dtype=LRO_REC_DTYPE)
     res = np.zeros(flows.size, dtype=LRO_RESULT_DTYPE)
-    _check(_lib.lvlip_lro_advance(flows.ctypes.data if flows.size else None, flows.size,
-                                  rec.ctypes.data if rec.size else None, rec.size,
-                                  res.ctypes.data if res.size else None), "lvlip_lro_advance")
+    _check(_lib.lvlip_lro_advance(_aptr(flows), flows.size, _aptr(rec), rec.size, _aptr(res)), "lvlip_lro_advance")
     return res
 
 
@@ -774,22 +789,17 @@ def lro_advance_dev(flows_t, rec_t, res_t=None, workspace_t=None, stream=None):
     Asynchronous on `stream` (default: current)."""
     import torch
 
-    n = rec_t.numel() * rec_t.element_size() // 16 if rec_t is not None else 0
-    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize if flows_t is not None else 0
+    n = _records(rec_t, 16)
+    nflows = _records(flows_t, LRO_FLOW_DTYPE.itemsize)
     device = flows_t.device if flows_t is not None else rec_t.device
-    if res_t is None:
-        res_t = torch.empty(LRO_RESULT_DTYPE.itemsize * max(nflows, 1), dtype=torch.uint8, device=device)
-    elif res_t.numel() * res_t.element_size() < LRO_RESULT_DTYPE.itemsize * nflows:
-        raise ValueError("res_t: 48 bytes per flow")
+    res_t = _result(res_t, "res_t", LRO_RESULT_DTYPE.itemsize, nflows, "flow", device)
     need = lro_advance_workspace_bytes(n, nflows) if n and nflows else 0
     if workspace_t is None and need:
         workspace_t = torch.empty(need, dtype=torch.uint8, device=device)
-    s = stream or torch.cuda.current_stream(device)
-    _check(_lib.lvlip_lro_advance_dev(flows_t.data_ptr() if nflows else None, nflows,
-                                      rec_t.data_ptr() if n else None, n, res_t.data_ptr(),
-                                      workspace_t.data_ptr() if workspace_t is not None else None,
-                                      workspace_t.numel() * workspace_t.element_size() if workspace_t is not None
-                                      else 0, s.cuda_stream), "lvlip_lro_advance_dev")
+    s = _stream(stream, device)
+    _check(_lib.lvlip_lro_advance_dev(_tptr(flows_t, nflows), nflows, _tptr(rec_t, n), n, res_t.data_ptr(),
+                                      _tptr(workspace_t), _records(workspace_t, 1), s.cuda_stream),
+           "lvlip_lro_advance_dev")
     return res_t[:LRO_RESULT_DTYPE.itemsize * nflows]
 
 
@@ -815,17 +825,13 @@ def ack_plan(tmpl: np.ndarray, flows: np.ndarray) -> int:
     """lvlip_ack_plan: validates the templates against the planned flows
     (template k answers flow k).  Returns out_bytes; ValueError for a refused
     plan."""
-    if tmpl.dtype != ACK_TMPL_DTYPE or not tmpl.flags.c_contiguous:
-        raise TypeError("tmpl: a contiguous ACK_TMPL_DTYPE array")
+    _planned(tmpl, ACK_TMPL_DTYPE, "tmpl: a contiguous ACK_TMPL_DTYPE array", writeable=False)
     flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
     if tmpl.size != flows.size:
         raise ValueError("one template per flow")
     out_bytes = ctypes.c_uint64(0)
-    n = int(_lib.lvlip_ack_plan(tmpl.ctypes.data if tmpl.size else None, flows.ctypes.data if flows.size else None,
-                                flows.size, ctypes.byref(out_bytes)))
-    if n == PLAN_MALFORMED:
-        raise ValueError("refused templates (header, max_sack, reserved, not the flow's reverse, overlapping slots, "
-                         "too many)")
+    _plan_ok(int(_lib.lvlip_ack_plan(_aptr(tmpl), _aptr(flows), flows.size, ctypes.byref(out_bytes))),
+             "refused templates (header, max_sack, reserved, not the flow's reverse, overlapping slots, too many)")
     return int(out_bytes.value)
 
 
@@ -840,14 +846,10 @@ def ack_cpu(tmpl: np.ndarray, flows: np.ndarray, res: np.ndarray, flags: int = 0
     res = np.ascontiguousarray(res, dtype=LRO_RESULT_DTYPE)
     if res.size != flows.size:
         raise ValueError("one result per flow")
-    if out is None:
-        out = np.zeros(out_bytes, dtype=np.uint8)
-    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < out_bytes:
-        raise ValueError("out: a contiguous uint8 array of at least the plan's out_bytes")
+    out = _out_u8(out, out_bytes)
     fd = np.zeros(flows.size, dtype=FRAME_DESC_DTYPE)
-    _check(_lib.lvlip_ack_cpu(tmpl.ctypes.data if tmpl.size else None, flows.ctypes.data if flows.size else None,
-                              res.ctypes.data if res.size else None, flows.size, flags, out.ctypes.data,
-                              fd.ctypes.data if fd.size else None), "lvlip_ack_cpu")
+    _check(_lib.lvlip_ack_cpu(_aptr(tmpl), _aptr(flows), _aptr(res), flows.size, flags, out.ctypes.data, _aptr(fd)),
+           "lvlip_ack_cpu")
     return out, fd
 
 
@@ -857,19 +859,13 @@ def ack_dev(tmpl_t, flows_t, res_t, flags: int, out_t, fd_t=None, stream=None):
     flow (what lro_advance_dev returned), out_t the frame buffer (at least the
     plan's out_bytes), fd_t (optional) 16 bytes per flow for the frame
     descriptors.  One launch on `stream` (default: current), asynchronous."""
-    import torch
-
-    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize
-    if tmpl_t.numel() * tmpl_t.element_size() < ACK_TMPL_DTYPE.itemsize * nflows:
-        raise ValueError("tmpl_t: 64 bytes per flow")
-    if res_t.numel() * res_t.element_size() < LRO_RESULT_DTYPE.itemsize * nflows:
-        raise ValueError("res_t: 48 bytes per flow")
-    if fd_t is not None and fd_t.numel() * fd_t.element_size() < 16 * nflows:
-        raise ValueError("fd_t: 16 bytes per flow")
-    s = stream or torch.cuda.current_stream(out_t.device)
+    nflows = _nbytes(flows_t) // LRO_FLOW_DTYPE.itemsize
+    _need(tmpl_t, "tmpl_t", ACK_TMPL_DTYPE.itemsize, nflows, "flow")
+    _need(res_t, "res_t", LRO_RESULT_DTYPE.itemsize, nflows, "flow")
+    _need(fd_t, "fd_t", 16, nflows, "flow", optional=True)
+    s = _stream(stream, out_t.device)
     _check(_lib.lvlip_ack_dev(tmpl_t.data_ptr(), flows_t.data_ptr(), res_t.data_ptr(), nflows, flags,
-                              out_t.data_ptr(), fd_t.data_ptr() if fd_t is not None else None, s.cuda_stream),
-           "lvlip_ack_dev")
+                              out_t.data_ptr(), _tptr(fd_t), s.cuda_stream), "lvlip_ack_dev")
 
 
 # ------------------------- f2 on the device: the ACK side and the retransmit --
@@ -886,17 +882,15 @@ assert SND_FLOW_DTYPE.itemsize == 32 and SND_RESULT_DTYPE.itemsize == 32
 def snd_plan(snd: np.ndarray):
     """lvlip_snd_plan: validates the flows' send sides and fills slot0 in
     place.  Returns (nslots, nfd); ValueError for a refused plan."""
-    if snd.dtype != SND_FLOW_DTYPE or not snd.flags.c_contiguous or not snd.flags.writeable:
-        raise TypeError("snd: a writeable contiguous SND_FLOW_DTYPE array")
+    _planned(snd, SND_FLOW_DTYPE, "snd: a writeable contiguous SND_FLOW_DTYPE array")
     nfd = ctypes.c_uint32(0)
-    n = int(_lib.lvlip_snd_plan(snd.ctypes.data if snd.size else None, snd.size, ctypes.byref(nfd)))
-    if n == PLAN_MALFORMED:
-        raise ValueError("refused send sides (reserved bytes, snd_nxt - snd_una, overlapping queues, too many)")
+    n = _plan_ok(int(_lib.lvlip_snd_plan(_aptr(snd), snd.size, ctypes.byref(nfd))),
+                 "refused send sides (reserved bytes, snd_nxt - snd_una, overlapping queues, too many)")
     return n, int(nfd.value)
 
 
 def _ring(base, fdescs, snd):
-    buf = base if isinstance(base, np.ndarray) and base.dtype == np.uint8 and base.flags.c_contiguous else _as_u8(base)
+    buf = _u8_inplace(base)
     fd = np.ascontiguousarray(fdescs, dtype=FRAME_DESC_DTYPE)
     ends = snd["seg0"].astype(np.uint64) + snd["nseg"]
     if ((snd["nseg"] > 0) & (ends > fd.size)).any():
@@ -918,12 +912,8 @@ def snd_cpu(flows: np.ndarray, snd: np.ndarray, rec: np.ndarray, base, fdescs: n
         raise ValueError("one send side per flow")
     buf, fd = _ring(base, fdescs, snd)
     res = np.zeros(flows.size, dtype=SND_RESULT_DTYPE)
-    keep = np.zeros(16, dtype=np.uint8)  # stands in for an empty ring: the call wants non-NULL pointers
-    _check(_lib.lvlip_snd_cpu(flows.ctypes.data if flows.size else None, snd.ctypes.data if snd.size else None,
-                              flows.size, rec.ctypes.data if rec.size else None, rec.size,
-                              buf.ctypes.data if buf.size else keep.ctypes.data,
-                              fd.ctypes.data if fd.size else keep.ctypes.data,
-                              res.ctypes.data if res.size else None), "lvlip_snd_cpu")
+    _check(_lib.lvlip_snd_cpu(_aptr(flows), _aptr(snd), flows.size, _aptr(rec), rec.size, _aptr(buf, True),
+                              _aptr(fd, True), _aptr(res)), "lvlip_snd_cpu")
     return res
 
 
@@ -933,35 +923,31 @@ def snd_dev(flows_t, snd_t, rec_t, base_t, fd_t, res_t=None, stream=None):
     record (what lro_dev returned), base_t / fd_t the TX ring and its
     descriptors.  Returns res_t, 32 bytes per flow (a new tensor unless
     given).  Asynchronous on `stream` (default: current)."""
-    import torch
-
-    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize
-    n = rec_t.numel() * rec_t.element_size() // 16 if rec_t is not None else 0
-    if snd_t.numel() * snd_t.element_size() < SND_FLOW_DTYPE.itemsize * nflows:
-        raise ValueError("snd_t: 32 bytes per flow")
-    if res_t is None:
-        res_t = torch.zeros(SND_RESULT_DTYPE.itemsize * max(nflows, 1), dtype=torch.uint8, device=flows_t.device)
-    elif res_t.numel() * res_t.element_size() < SND_RESULT_DTYPE.itemsize * nflows:
-        raise ValueError("res_t: 32 bytes per flow")
-    s = stream or torch.cuda.current_stream(flows_t.device)
-    _check(_lib.lvlip_snd_dev(flows_t.data_ptr(), snd_t.data_ptr(), nflows, rec_t.data_ptr() if n else None, n,
-                              base_t.data_ptr(), fd_t.data_ptr(), res_t.data_ptr(), s.cuda_stream), "lvlip_snd_dev")
+    nflows = _nbytes(flows_t) // LRO_FLOW_DTYPE.itemsize
+    n = _records(rec_t, 16)
+    _need(snd_t, "snd_t", SND_FLOW_DTYPE.itemsize, nflows, "flow")
+    res_t = _result(res_t, "res_t", SND_RESULT_DTYPE.itemsize, nflows, "flow", flows_t.device, zeroed=True)
+    s = _stream(stream, flows_t.device)
+    _check(_lib.lvlip_snd_dev(flows_t.data_ptr(), snd_t.data_ptr(), nflows, _tptr(rec_t, n), n, base_t.data_ptr(),
+                              fd_t.data_ptr(), res_t.data_ptr(), s.cuda_stream), "lvlip_snd_dev")
     return res_t[:SND_RESULT_DTYPE.itemsize * nflows]
 
 
-def rtx_cpu(flows: np.ndarray, lro_res, snd: np.ndarray, snd_res, base: np.ndarray, fdescs: np.ndarray) -> np.ndarray:
-    """lvlip_rtx_cpu: rewrites the live frames at the head of every queue IN
-    PLACE in `base` (a writeable contiguous uint8 array).  lro_res
-    (LRO_RESULT_DTYPE per flow) and snd_res (SND_RESULT_DTYPE per flow) may be
-    None.  Returns fd_out, FRAME_DESC_DTYPE per slot ({0, 0, 0} = no frame)."""
+def _rtx_cpu(flows, lro_res, snd, snd_res, sacked, base, fdescs, selective: bool):
+    """rtx_cpu and, with `selective`, rtx_sack_cpu: lvlip_rtx_sack_cpu takes
+    lvlip_rtx_cpu's arguments plus the scoreboard and the picks.  Returns
+    (fd_out, pick); pick is None unless selective."""
     flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
     snd = np.ascontiguousarray(snd, dtype=SND_FLOW_DTYPE)
     if snd.size != flows.size:
         raise ValueError("one send side per flow")
-    if not isinstance(base, np.ndarray) or base.dtype != np.uint8 or not base.flags.c_contiguous or \
-            not base.flags.writeable:
+    if not _is_u8(base, writeable=True):
         raise TypeError("base: a writeable contiguous uint8 array (the ring is rewritten in place)")
     _, fd = _ring(base, fdescs, snd)
+    if sacked is not None:
+        sacked = np.ascontiguousarray(sacked, dtype=np.uint8)
+        if sacked.size < fd.size:
+            raise ValueError("sacked: one byte per fd entry")
     if lro_res is not None:
         lro_res = np.ascontiguousarray(lro_res, dtype=LRO_RESULT_DTYPE)
     if snd_res is not None:
@@ -970,15 +956,43 @@ def rtx_cpu(flows: np.ndarray, lro_res, snd: np.ndarray, snd_res, base: np.ndarr
         raise ValueError("one result per flow")
     nslots = int(snd["rtx"].astype(np.uint64).sum()) if snd.size else 0
     fd_out = np.zeros(nslots, dtype=FRAME_DESC_DTYPE)
-    keep = np.zeros(16, dtype=np.uint8)
-    _check(_lib.lvlip_rtx_cpu(flows.ctypes.data if flows.size else None,
-                              lro_res.ctypes.data if lro_res is not None and lro_res.size else None,
-                              snd.ctypes.data if snd.size else None,
-                              snd_res.ctypes.data if snd_res is not None and snd_res.size else None,
-                              flows.size, nslots, base.ctypes.data if base.size else keep.ctypes.data,
-                              fd.ctypes.data if fd.size else keep.ctypes.data,
-                              fd_out.ctypes.data if fd_out.size else None), "lvlip_rtx_cpu")
-    return fd_out
+    head = (_aptr(flows), _aptr(lro_res), _aptr(snd), _aptr(snd_res))
+    tail = (flows.size, nslots, _aptr(base, True), _aptr(fd, True), _aptr(fd_out))
+    if not selective:
+        _check(_lib.lvlip_rtx_cpu(*head, *tail), "lvlip_rtx_cpu")
+        return fd_out, None
+    pick = np.full(nslots, SACK_NO_PICK, dtype=np.uint32)
+    _check(_lib.lvlip_rtx_sack_cpu(*head, _aptr(sacked), *tail, _aptr(pick)), "lvlip_rtx_sack_cpu")
+    return fd_out, pick
+
+
+def _rtx_dev(flows_t, lro_res_t, snd_t, snd_res_t, sacked_t, nslots, base_t, fd_t, fd_out_t, pick_t, stream,
+             selective: bool):
+    """rtx_dev and, with `selective`, rtx_sack_dev, as _rtx_cpu."""
+    nflows = _nbytes(flows_t) // LRO_FLOW_DTYPE.itemsize
+    _need(snd_t, "snd_t", SND_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(lro_res_t, "lro_res_t", LRO_RESULT_DTYPE.itemsize, nflows, "flow", optional=True)
+    _need(snd_res_t, "snd_res_t", SND_RESULT_DTYPE.itemsize, nflows, "flow", optional=True)
+    fd_out_t = _result(fd_out_t, "fd_out_t", 16, nslots, "slot", base_t.device)
+    if selective:
+        pick_t = _result(pick_t, "pick_t", 4, nslots, "slot", base_t.device)
+    s = _stream(stream, base_t.device)
+    head = (flows_t.data_ptr(), _tptr(lro_res_t), snd_t.data_ptr(), _tptr(snd_res_t))
+    tail = (nflows, nslots, base_t.data_ptr(), fd_t.data_ptr(), fd_out_t.data_ptr())
+    if not selective:
+        _check(_lib.lvlip_rtx_dev(*head, *tail, s.cuda_stream), "lvlip_rtx_dev")
+        return fd_out_t[:16 * nslots], None
+    _check(_lib.lvlip_rtx_sack_dev(*head, _tptr(sacked_t), *tail, pick_t.data_ptr(), s.cuda_stream),
+           "lvlip_rtx_sack_dev")
+    return fd_out_t[:16 * nslots], pick_t[:4 * nslots]
+
+
+def rtx_cpu(flows: np.ndarray, lro_res, snd: np.ndarray, snd_res, base: np.ndarray, fdescs: np.ndarray) -> np.ndarray:
+    """lvlip_rtx_cpu: rewrites the live frames at the head of every queue IN
+    PLACE in `base` (a writeable contiguous uint8 array).  lro_res
+    (LRO_RESULT_DTYPE per flow) and snd_res (SND_RESULT_DTYPE per flow) may be
+    None.  Returns fd_out, FRAME_DESC_DTYPE per slot ({0, 0, 0} = no frame)."""
+    return _rtx_cpu(flows, lro_res, snd, snd_res, None, base, fdescs, False)[0]
 
 
 def rtx_dev(flows_t, lro_res_t, snd_t, snd_res_t, nslots: int, base_t, fd_t, fd_out_t=None, stream=None):
@@ -987,25 +1001,7 @@ def rtx_dev(flows_t, lro_res_t, snd_t, snd_res_t, nslots: int, base_t, fd_t, fd_
     per flow) may be None; nslots is what snd_plan returned.  Returns
     fd_out_t, 16 bytes per slot (a new tensor unless given).  Asynchronous on
     `stream` (default: current)."""
-    import torch
-
-    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize
-    if snd_t.numel() * snd_t.element_size() < SND_FLOW_DTYPE.itemsize * nflows:
-        raise ValueError("snd_t: 32 bytes per flow")
-    if lro_res_t is not None and lro_res_t.numel() * lro_res_t.element_size() < LRO_RESULT_DTYPE.itemsize * nflows:
-        raise ValueError("lro_res_t: 48 bytes per flow")
-    if snd_res_t is not None and snd_res_t.numel() * snd_res_t.element_size() < SND_RESULT_DTYPE.itemsize * nflows:
-        raise ValueError("snd_res_t: 32 bytes per flow")
-    if fd_out_t is None:
-        fd_out_t = torch.empty(16 * max(nslots, 1), dtype=torch.uint8, device=base_t.device)
-    elif fd_out_t.numel() * fd_out_t.element_size() < 16 * nslots:
-        raise ValueError("fd_out_t: 16 bytes per slot")
-    s = stream or torch.cuda.current_stream(base_t.device)
-    _check(_lib.lvlip_rtx_dev(flows_t.data_ptr(), lro_res_t.data_ptr() if lro_res_t is not None else None,
-                              snd_t.data_ptr(), snd_res_t.data_ptr() if snd_res_t is not None else None, nflows,
-                              nslots, base_t.data_ptr(), fd_t.data_ptr(), fd_out_t.data_ptr(), s.cuda_stream),
-           "lvlip_rtx_dev")
-    return fd_out_t[:16 * nslots]
+    return _rtx_dev(flows_t, lro_res_t, snd_t, snd_res_t, None, nslots, base_t, fd_t, fd_out_t, None, stream, False)[0]
 
 
 # struct lvlip_sack_result (include/lvlip_skb.h), 16 B
@@ -1031,29 +1027,21 @@ def sack_cpu(flows: np.ndarray, snd: np.ndarray, rec: np.ndarray, ack_base, ack_
     rec = np.ascontiguousarray(rec, dtype=LRO_REC_DTYPE)
     if snd.size != flows.size:
         raise ValueError("one send side per flow")
-    if not isinstance(sacked, np.ndarray) or sacked.dtype != np.uint8 or not sacked.flags.c_contiguous or \
-            not sacked.flags.writeable:
+    if not _is_u8(sacked, writeable=True):
         raise TypeError("sacked: a writeable contiguous uint8 array (the scoreboard is marked in place)")
     buf, fd = _ring(base, fdescs, snd)
     if sacked.size < fd.size:
         raise ValueError("sacked: one byte per fd entry")
-    abuf = ack_base if isinstance(ack_base, np.ndarray) and ack_base.dtype == np.uint8 and \
-        ack_base.flags.c_contiguous else _as_u8(ack_base)
+    abuf = _u8_inplace(ack_base)
     afd = np.ascontiguousarray(ack_fdescs, dtype=FRAME_DESC_DTYPE)
     if afd.size != rec.size:
         raise ValueError("one record per ACK frame")
     if (afd["offset"] + afd["len"].astype(np.uint64) > abuf.size).any():
         raise ValueError("an ACK frame lies past ack_base")
     res = np.zeros(flows.size, dtype=SACK_RESULT_DTYPE)
-    keep = np.zeros(16, dtype=np.uint8)  # stands in for an empty buffer: the call wants non-NULL pointers
-    _check(_lib.lvlip_sack_cpu(flows.ctypes.data if flows.size else None, snd.ctypes.data if snd.size else None,
-                               flows.size, rec.ctypes.data if rec.size else None,
-                               abuf.ctypes.data if abuf.size else keep.ctypes.data,
-                               afd.ctypes.data if afd.size else None, rec.size,
-                               buf.ctypes.data if buf.size else keep.ctypes.data,
-                               fd.ctypes.data if fd.size else keep.ctypes.data,
-                               sacked.ctypes.data if sacked.size else keep.ctypes.data,
-                               res.ctypes.data if res.size else None), "lvlip_sack_cpu")
+    _check(_lib.lvlip_sack_cpu(_aptr(flows), _aptr(snd), flows.size, _aptr(rec), _aptr(abuf, True), _aptr(afd),
+                               rec.size, _aptr(buf, True), _aptr(fd, True), _aptr(sacked, True), _aptr(res)),
+           "lvlip_sack_cpu")
     return res
 
 
@@ -1067,25 +1055,21 @@ def sack_dev(flows_t, snd_t, rec_t, ack_base_t, ack_fd_t, base_t, fd_t, sacked_t
     given).  Asynchronous on `stream` (default: current)."""
     import torch
 
-    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize
-    n = rec_t.numel() * rec_t.element_size() // 16 if rec_t is not None else 0
-    if snd_t.numel() * snd_t.element_size() < SND_FLOW_DTYPE.itemsize * nflows:
-        raise ValueError("snd_t: 32 bytes per flow")
-    if n and ack_fd_t.numel() * ack_fd_t.element_size() < 16 * n:
-        raise ValueError("ack_fd_t: 16 bytes per record")
-    if res_t is None:
-        res_t = torch.zeros(SACK_RESULT_DTYPE.itemsize * max(nflows, 1), dtype=torch.uint8, device=flows_t.device)
-    elif res_t.numel() * res_t.element_size() < SACK_RESULT_DTYPE.itemsize * nflows:
-        raise ValueError("res_t: 16 bytes per flow")
+    nflows = _nbytes(flows_t) // LRO_FLOW_DTYPE.itemsize
+    n = _records(rec_t, 16)
+    _need(snd_t, "snd_t", SND_FLOW_DTYPE.itemsize, nflows, "flow")
+    if n:
+        _need(ack_fd_t, "ack_fd_t", 16, n, "record")
+    res_t = _result(res_t, "res_t", SACK_RESULT_DTYPE.itemsize, nflows, "flow", flows_t.device, zeroed=True)
     if workspace_t is None:
         workspace_t = torch.empty(max(sack_workspace_bytes(n, nflows), 256), dtype=torch.uint8,
                                   device=flows_t.device)
-    s = stream or torch.cuda.current_stream(flows_t.device)
-    _check(_lib.lvlip_sack_dev(flows_t.data_ptr(), snd_t.data_ptr(), nflows, rec_t.data_ptr() if n else None,
+    s = _stream(stream, flows_t.device)
+    # an empty batch sends rec, ack_base and ack_fd down as NULL, whatever the caller gave
+    _check(_lib.lvlip_sack_dev(flows_t.data_ptr(), snd_t.data_ptr(), nflows, _tptr(rec_t, n),
                                ack_base_t.data_ptr() if n else None, ack_fd_t.data_ptr() if n else None, n,
                                base_t.data_ptr(), fd_t.data_ptr(), sacked_t.data_ptr(), res_t.data_ptr(),
-                               workspace_t.data_ptr(), workspace_t.numel() * workspace_t.element_size(),
-                               s.cuda_stream), "lvlip_sack_dev")
+                               workspace_t.data_ptr(), _nbytes(workspace_t), s.cuda_stream), "lvlip_sack_dev")
     return res_t[:SACK_RESULT_DTYPE.itemsize * nflows]
 
 
@@ -1094,38 +1078,7 @@ def rtx_sack_cpu(flows: np.ndarray, lro_res, snd: np.ndarray, snd_res, sacked, b
     byte in `sacked` (uint8 per fd index, or None) is 0.  Rewrites `base` in
     place.  Returns (fd_out, pick): FRAME_DESC_DTYPE and the uint32 fd index
     per slot (SACK_NO_PICK for a dead slot)."""
-    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
-    snd = np.ascontiguousarray(snd, dtype=SND_FLOW_DTYPE)
-    if snd.size != flows.size:
-        raise ValueError("one send side per flow")
-    if not isinstance(base, np.ndarray) or base.dtype != np.uint8 or not base.flags.c_contiguous or \
-            not base.flags.writeable:
-        raise TypeError("base: a writeable contiguous uint8 array (the ring is rewritten in place)")
-    _, fd = _ring(base, fdescs, snd)
-    if sacked is not None:
-        sacked = np.ascontiguousarray(sacked, dtype=np.uint8)
-        if sacked.size < fd.size:
-            raise ValueError("sacked: one byte per fd entry")
-    if lro_res is not None:
-        lro_res = np.ascontiguousarray(lro_res, dtype=LRO_RESULT_DTYPE)
-    if snd_res is not None:
-        snd_res = np.ascontiguousarray(snd_res, dtype=SND_RESULT_DTYPE)
-    if any(r is not None and r.size != flows.size for r in (lro_res, snd_res)):
-        raise ValueError("one result per flow")
-    nslots = int(snd["rtx"].astype(np.uint64).sum()) if snd.size else 0
-    fd_out = np.zeros(nslots, dtype=FRAME_DESC_DTYPE)
-    pick = np.full(nslots, SACK_NO_PICK, dtype=np.uint32)
-    keep = np.zeros(16, dtype=np.uint8)
-    _check(_lib.lvlip_rtx_sack_cpu(flows.ctypes.data if flows.size else None,
-                                   lro_res.ctypes.data if lro_res is not None and lro_res.size else None,
-                                   snd.ctypes.data if snd.size else None,
-                                   snd_res.ctypes.data if snd_res is not None and snd_res.size else None,
-                                   sacked.ctypes.data if sacked is not None and sacked.size else None,
-                                   flows.size, nslots, base.ctypes.data if base.size else keep.ctypes.data,
-                                   fd.ctypes.data if fd.size else keep.ctypes.data,
-                                   fd_out.ctypes.data if fd_out.size else None,
-                                   pick.ctypes.data if pick.size else None), "lvlip_rtx_sack_cpu")
-    return fd_out, pick
+    return _rtx_cpu(flows, lro_res, snd, snd_res, sacked, base, fdescs, True)
 
 
 def rtx_sack_dev(flows_t, lro_res_t, snd_t, snd_res_t, sacked_t, nslots: int, base_t, fd_t, fd_out_t=None,
@@ -1135,30 +1088,8 @@ def rtx_sack_dev(flows_t, lro_res_t, snd_t, snd_res_t, sacked_t, nslots: int, ba
     lro_res_t and snd_res_t may be None.  Returns (fd_out_t, pick_t): 16 and 4
     bytes per slot (new tensors unless given).  Asynchronous on `stream`
     (default: current)."""
-    import torch
-
-    nflows = flows_t.numel() * flows_t.element_size() // LRO_FLOW_DTYPE.itemsize
-    if snd_t.numel() * snd_t.element_size() < SND_FLOW_DTYPE.itemsize * nflows:
-        raise ValueError("snd_t: 32 bytes per flow")
-    if lro_res_t is not None and lro_res_t.numel() * lro_res_t.element_size() < LRO_RESULT_DTYPE.itemsize * nflows:
-        raise ValueError("lro_res_t: 48 bytes per flow")
-    if snd_res_t is not None and snd_res_t.numel() * snd_res_t.element_size() < SND_RESULT_DTYPE.itemsize * nflows:
-        raise ValueError("snd_res_t: 32 bytes per flow")
-    if fd_out_t is None:
-        fd_out_t = torch.empty(16 * max(nslots, 1), dtype=torch.uint8, device=base_t.device)
-    elif fd_out_t.numel() * fd_out_t.element_size() < 16 * nslots:
-        raise ValueError("fd_out_t: 16 bytes per slot")
-    if pick_t is None:
-        pick_t = torch.empty(4 * max(nslots, 1), dtype=torch.uint8, device=base_t.device)
-    elif pick_t.numel() * pick_t.element_size() < 4 * nslots:
-        raise ValueError("pick_t: 4 bytes per slot")
-    s = stream or torch.cuda.current_stream(base_t.device)
-    _check(_lib.lvlip_rtx_sack_dev(flows_t.data_ptr(), lro_res_t.data_ptr() if lro_res_t is not None else None,
-                                   snd_t.data_ptr(), snd_res_t.data_ptr() if snd_res_t is not None else None,
-                                   sacked_t.data_ptr() if sacked_t is not None else None, nflows, nslots,
-                                   base_t.data_ptr(), fd_t.data_ptr(), fd_out_t.data_ptr(), pick_t.data_ptr(),
-                                   s.cuda_stream), "lvlip_rtx_sack_dev")
-    return fd_out_t[:16 * nslots], pick_t[:4 * nslots]
+    return _rtx_dev(flows_t, lro_res_t, snd_t, snd_res_t, sacked_t, nslots, base_t, fd_t, fd_out_t, pick_t, stream,
+                    True)
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
@@ -1196,7 +1127,7 @@ def frames_variant_dev(mode: int, variant: int, base, fdescs, stream=None):
 
     n, fd = _frames_dev(base, fdescs)
     out8 = torch.empty(max(n, 1), dtype=torch.uint8, device=base.device)
-    s = stream or torch.cuda.current_stream(base.device)
+    s = _stream(stream, base.device)
     _check(lab().lvlip_lab_frames_dev(mode, variant, base.data_ptr(), fd.data_ptr(), n, out8.data_ptr(),
                                       s.cuda_stream), "lvlip_lab_frames_dev")
     return out8[:n]

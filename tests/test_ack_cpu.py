@@ -22,6 +22,7 @@ import pytest
 
 import lvlip
 import pyoracle
+from tcp_model import _bswap16, _fold, lost_carry_seed  # noqa: F401  (other tests import them from here)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "ack_ref.json")
@@ -30,22 +31,7 @@ M32 = 0xFFFFFFFF
 ETH = bytes.fromhex("0a1b2c3d4e5f000c296d5025") + b"\x08\x00"
 
 
-def _bswap16(x: int) -> int:
-    return ((x & 0xFF) << 8) | ((x >> 8) & 0xFF)
-
-
-def _fold(x: int) -> int:
-    while x >> 16:
-        x = (x & 0xFFFF) + (x >> 16)
-    return x
-
-
 # --------------------------------------------------------------- the model --
-
-def lost_carry_seed(saddr: bytes, daddr: bytes, l4len: int) -> int:
-    """src/tcp.c:92-95: the addresses as u32 words, added in a u32."""
-    return (int.from_bytes(saddr, "little") + int.from_bytes(daddr, "little") + _bswap16(6) + _bswap16(l4len)) & M32
-
 
 def model_frame(hdr: bytes, rcv_nxt: int, delivered: int, nsack: int, sack, max_sack: int, seed_fn=lost_carry_seed):
     """The ACK frame of one flow from the header's text."""

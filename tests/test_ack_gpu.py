@@ -15,7 +15,9 @@ import numpy as np
 import pytest
 import torch
 
+import devbuf
 import lvlip
+from devbuf import _t
 from test_ack_cpu import (CANARY, assert_same_out, golden_compared, golden_inputs, hand, make_flows, make_tmpl,
                           model_run, random_res)
 
@@ -30,13 +32,7 @@ GUARD = 64
 
 @pytest.fixture(scope="module")
 def dev():
-    if not torch.cuda.is_available() or lvlip.device_count() == 0:
-        pytest.fail("the gpu tests need a HIP device")
-    return torch.device("cuda", 0)
-
-
-def _t(a: np.ndarray, dev):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    return devbuf.device()
 
 
 @functools.lru_cache(maxsize=None)

@@ -29,9 +29,11 @@ import numpy as np
 import pytest
 import torch
 
+import devbuf
 import lvlip
 import pyoracle
 import workloads
+from devbuf import CANARY, _t, guarded, unguard
 from test_ack_cpu import make_flows, make_tmpl, random_res
 from test_lro_cpu import ME, PEER, tcp_frame
 from test_skb_cpu import _rx_cases
@@ -46,7 +48,6 @@ SHIFT = TOP - 2 * MiB         # host offset + SHIFT = device offset, for the hig
 LOW0 = MiB // 2               # low objects from here; [0, LOW0) is where the 32-bit aliases land
 HIGH0 = 2 * MiB + (16 << 10)  # host offset of 2^32 + 16 KiB: the first high object that does not straddle
 HIGH1 = 2 * MiB + LOW0
-CANARY, GUARD = 0x5A, 64
 SIZES = (1, 2, 3, 536, 1460)
 
 
@@ -132,26 +133,10 @@ class Far:
 
 @pytest.fixture(scope="module")
 def zone():
-    if not torch.cuda.is_available() or lvlip.device_count() == 0:
-        pytest.fail("the gpu tests need a HIP device")
-    z = Far(torch.device("cuda", 0))
+    z = Far(devbuf.device())
     yield z
     z.base = z.big = None
     torch.cuda.empty_cache()
-
-
-def _t(a: np.ndarray, dev):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
-
-
-def guarded(nbytes: int, dev):
-    return torch.full((nbytes + GUARD,), CANARY, dtype=torch.uint8, device=dev)
-
-
-def unguard(t, nbytes: int, dtype):
-    a = t.cpu().numpy()
-    assert (a[nbytes:] == CANARY).all(), "written behind the output"
-    return a[:nbytes].view(dtype)
 
 
 def blank() -> np.ndarray:

@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 import lvlip
-from test_far_offsets_gpu import (MiB, Lay, _t, assert_mixed, blank, far, fd_far, fd_near, guarded, unguard,
+from devbuf import _t, guarded, unguard
+from test_far_offsets_gpu import (MiB, Lay, assert_mixed, blank, far, fd_far, fd_near,
                                   zone)  # noqa: F401  (zone: the module's fixture)
 from test_sack_cpu import NO_PICK, make_acks
 from test_snd_cpu import Case

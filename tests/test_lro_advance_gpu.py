@@ -17,15 +17,15 @@ import numpy as np
 import pytest
 import torch
 
+import devbuf
 import lvlip
+from devbuf import ALIGNED_GUARD as GUARD, CANARY, _t, guarded_aligned as guarded
 from test_lro_cpu import FLOW_COUNTS, N_LIST, case, fixture_inputs, model_advance, plan_flows, result_tuples
 
 pytestmark = pytest.mark.gpu
 
 TILE = 256
 SPINE = 64
-CANARY = 0x5A
-GUARD = 256
 NFLOWS = 10
 SIZES = (1, 255, 256, 257, 3 * TILE + 1, 40000)
 assert SIZES[-1] > TILE * SPINE
@@ -34,20 +34,7 @@ STATUSES = (0, 2, 3, 4, 5, 6, 7, 8, 9, 16, 17, 18, 19, 20, 21)  # every value bu
 
 @pytest.fixture(scope="module")
 def dev():
-    if not torch.cuda.is_available() or lvlip.device_count() == 0:
-        pytest.fail("the gpu tests need a HIP device")
-    return torch.device("cuda", 0)
-
-
-def _t(a: np.ndarray, dev):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
-
-
-def guarded(nbytes: int, dev):
-    """A 256-B aligned tensor of nbytes + GUARD canary bytes."""
-    t = torch.full((nbytes + GUARD + 256,), CANARY, dtype=torch.uint8, device=dev)
-    skip = -t.data_ptr() % 256
-    return t[skip:skip + nbytes + GUARD]
+    return devbuf.device()
 
 
 def advance_dev(flows: np.ndarray, rec: np.ndarray, dev, stream=None) -> np.ndarray:

@@ -24,6 +24,7 @@ import pytest
 import lvlip
 import pyoracle
 import ref_rx_cases
+from tcp_model import _bswap16, _fold, pseudo_rfc
 from test_tso_cpu import template as tso_template
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,22 +40,6 @@ FLOW_COUNTS = (1, 3, 17)
 
 
 # -------------------------------------------------------------- the frames --
-
-def _fold(x: int) -> int:
-    while x >> 16:
-        x = (x & 0xFFFF) + (x >> 16)
-    return x
-
-
-def _bswap16(x: int) -> int:
-    return ((x & 0xFF) << 8) | ((x >> 8) & 0xFF)
-
-
-def pseudo_rfc(saddr: bytes, daddr: bytes, l4len: int) -> int:
-    """RFC 1071 pseudo header over the header's words as stored, carries kept."""
-    s = sum(struct.unpack("<4H", saddr + daddr))
-    return s + _bswap16(6) + _bswap16(l4len)
-
 
 def tcp_frame(payload: bytes, seq: int, sport: int = 40001, dport: int = 8000, saddr: bytes = PEER,
               daddr: bytes = ME, ack: int = 0x01020304, flags: int = 0x10, ihl: int = 5, hl: int = 5,

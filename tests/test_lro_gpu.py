@@ -10,7 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+import devbuf
 import lvlip
+from devbuf import _t
 from test_lro_cpu import (CANARY, FLOW_COUNTS, FRAME_MODS, N_LIST, OUT_MODS, assert_same_out, assert_same_rec, case,
                           expected, fixture_inputs, flow_kw, model_advance, plan_flows, result_tuples, tcp_frame)
 from test_tso_cpu import template as tso_template
@@ -20,13 +22,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def dev():
-    if not torch.cuda.is_available() or lvlip.device_count() == 0:
-        pytest.fail("the gpu tests need a HIP device")
-    return torch.device("cuda", 0)
-
-
-def _t(a: np.ndarray, dev):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    return devbuf.device()
 
 
 def run_dev(buf, fd, flows, flags, out_size, dev, stream=None):

@@ -21,10 +21,12 @@ import numpy as np
 import pytest
 import torch
 
+import devbuf
 import lvlip
+from devbuf import _t
 from test_sack_cpu import NO_PICK, ack_frame, golden_check, in_queues, make_acks, marks_case, queues, sack_opt
 from test_snd_cpu import CANARY, GUARD, M32, Case, hand
-from test_snd_gpu import MSS, Link, _t
+from test_snd_gpu import MSS, Link
 
 pytestmark = pytest.mark.gpu
 
@@ -33,9 +35,7 @@ SACK_TILE, SACK_WAVES, SACK_Y, SACK_Y_MIN, SACK_GRID = 256, 4, 1024, 8, 1 << 17 
 
 @pytest.fixture(scope="module")
 def dev():
-    if not torch.cuda.is_available() or lvlip.device_count() == 0:
-        pytest.fail("the gpu tests need a HIP device")
-    return torch.device("cuda", 0)
+    return devbuf.device()
 
 
 def run_sack_dev(c, rec, aring, afd, dev, sacked=None, stream=None):

@@ -34,6 +34,7 @@ import pytest
 
 import lvlip
 import pyoracle
+from tcp_model import lost_carry_seed
 from test_ack_cpu import ETH, make_flows, template_hdr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -685,8 +686,7 @@ PAD_SEED = 1  # Foreign asserts what this has to achieve: every padded frame's s
 def _seed(fr: bytes, l4len: int) -> int:
     """tcp_udp_checksum's start value (src/tcp.c:87-98): u32 adds of the
     addresses as stored, the carry out of bit 31 lost."""
-    saddr, daddr = struct.unpack_from("<II", fr, 26)
-    return (saddr + daddr + 0x0600 + (((l4len & 0xFF) << 8) | (l4len >> 8 & 0xFF))) & M32
+    return lost_carry_seed(bytes(fr[26:30]), bytes(fr[30:34]), l4len)
 
 
 def foreign_frame(rng, flow, seq: int, sp: Spec) -> bytes:

@@ -21,7 +21,9 @@ import numpy as np
 import pytest
 import torch
 
+import devbuf
 import lvlip
+from devbuf import _t
 from test_snd_cpu import (CANARY, FOREIGN, GUARD, M32, Case, _rec, check_rtx_foreign, fixture, foreign, foreign_records,
                           golden_resend, golden_ring, golden_snd, head_acks, head_named_check, make_records, model_rtx,
                           model_snd, rtx_inputs)
@@ -31,13 +33,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def dev():
-    if not torch.cuda.is_available() or lvlip.device_count() == 0:
-        pytest.fail("the gpu tests need a HIP device")
-    return torch.device("cuda", 0)
-
-
-def _t(a: np.ndarray, dev):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    return devbuf.device()
 
 
 @functools.lru_cache(maxsize=None)

@@ -20,6 +20,7 @@ import pytest
 
 import lvlip
 import pyoracle
+from tcp_model import _bswap16, lost_carry_seed
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "tso_ref.json")
@@ -45,15 +46,10 @@ def template(saddr=(10, 0, 0, 4), daddr=(10, 0, 0, 5), sport=40001, dport=8000, 
     return eth + ip + tcp
 
 
-def _bswap16(x: int) -> int:
-    return ((x & 0xFF) << 8) | ((x >> 8) & 0xFF)
-
-
 def seed_of(hdr: bytes, l4: int) -> int:
     """src/tcp.c:92-95 on the template's network-order address words: u32
     adds, the carry out of bit 31 lost."""
-    sa, da = struct.unpack("<II", hdr[26:34])
-    return (sa + da + _bswap16(6) + _bswap16(l4)) & 0xFFFFFFFF
+    return lost_carry_seed(hdr[26:30], hdr[30:34], l4)
 
 
 def build_frame(hdr: bytes, data: bytes, seq_add: int, last: bool) -> bytes:

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import devbuf
 import lvlip
 from test_tso_cpu import (ALL_CASES, CANARY, assert_same, fixture, fixture_case, fixture_frames, multi_case,
                           parity_case)
@@ -17,9 +18,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def dev():
-    if not torch.cuda.is_available() or lvlip.device_count() == 0:
-        pytest.fail("the gpu tests need a HIP device")
-    return torch.device("cuda", 0)
+    return devbuf.device()
 
 
 def run_dev(case, dev, stream=None, with_fd=True):
