@@ -465,6 +465,98 @@ size_t lvlip_lro_advance_workspace_bytes(uint32_t n, uint32_t nflows);
 int lvlip_lro_advance_dev(const lvlip_lro_flow *f, uint32_t nflows, const lvlip_lro_rec *rec, uint32_t n,
                           lvlip_lro_result *res, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- f1 on the device: state across batches --------------------------------- */
+
+/* The calls above work on one batch.  These carry a connection over to the
+ * next one, so that a transfer of many rounds runs with record arrays of one
+ * round's size and, on the device, with no host step between rounds:
+ *   lvlip_lro_* -> lvlip_lro_advance_carry* (prev = the results of the round
+ *   before) -> lvlip_ack_* -> lvlip_lro_next_*, and on the sender
+ *   lvlip_snd_* -> lvlip_sack_* / lvlip_rtx* -> lvlip_snd_next_*.
+ *
+ * lvlip_lro_advance_carry is lvlip_lro_advance with one more source of
+ * intervals.  prev[k] is the result an earlier call left for flow k; its
+ * sack[] holds absolute sequence numbers, so it survives a change of rcv_nxt.
+ *
+ * Carried blocks.  For flow k and j < min(prev[k].nsack, 4), against f[k] as it
+ * is AT THE CALL: l = (sack[j].left - f[k].rcv_nxt) mod 2^32, r =
+ * (sack[j].right - f[k].rcv_nxt) mod 2^32.  The block counts when l < r <=
+ * f[k].rcv_wnd and joins the flow's union as [l, r).  A block that is stale
+ * (behind rcv_nxt), empty, straddling rcv_nxt or ending beyond the window is
+ * ignored, and so is every other field of prev: a crafted prev (nsack 7, any
+ * edges) changes values, never an address.
+ *
+ * Results.  delivered, nsack and sack[] describe the union of the PLACED
+ * records and the carried blocks; placed counts records only.  A flow with a
+ * carry and no record still gets its islands.  With n == 0 and a prev the call
+ * is not a zero fill: the results are the union of the carried blocks.  With
+ * prev == NULL all 48 bytes of every result equal lvlip_lro_advance's, for any
+ * record array.  prev == res is allowed (in place).
+ *
+ * What is remembered.  The carry is the four islands a result reports.  A
+ * fifth island of a flow is FORGOTTEN from one call to the next: its bytes stay
+ * in `out`, nothing accounts for them, and the peer sends them again (they were
+ * never the subject of a SACK block, and RFC 2018 section 8 lets a receiver
+ * renege in any case).  Within one call any number of islands is united as
+ * before.
+ *
+ * lvlip_lro_advance_carry: host only.  Returns as lvlip_lro_advance; prev may
+ * be NULL.  Reentrant. */
+int lvlip_lro_advance_carry(const lvlip_lro_flow *f, uint32_t nflows, const lvlip_lro_rec *rec, uint32_t n,
+                            const lvlip_lro_result *prev, lvlip_lro_result *res);
+
+/* Bytes of device workspace lvlip_lro_advance_carry_dev needs: what
+ * lvlip_lro_advance_dev's needs, for n + 4 nflows elements with 4-B lengths,
+ * and 4 bytes per flow (24 (n + 4 nflows) and a little), and never less than
+ * lvlip_lro_advance_workspace_bytes(n, nflows).  Unlike that call it is not 0
+ * for n == 0: the carried blocks are elements too.  Returns 0 for nflows == 0
+ * or above LVLIP_LRO_MAX_FLOWS, for n + 4 nflows above LVLIP_MAX_BATCH, and when
+ * there is no device.  May initialise the HIP runtime. */
+size_t lvlip_lro_advance_carry_workspace_bytes(uint32_t n, uint32_t nflows);
+
+/* lvlip_lro_advance_carry on the device, every byte of res equal to the host
+ * form's: lvlip_lro_advance_dev's pipeline over n + 4 nflows elements, the key
+ * step also turning block j of prev[k] into element n + 4 k + j, with 4-B
+ * lengths through the sort and the scans (a carried block is up to 2^30 bytes
+ * long).  Asynchronous on `stream`: no allocation, no device-to-host copy, no
+ * synchronisation; rec and f are only read, and so is prev unless it is res.
+ * Pointers and alignments as for lvlip_lro_advance_dev, prev 16-B aligned.
+ * nflows == 0 is a no-op.  LVLIP_EINVAL before any HIP call: the refusals of
+ * lvlip_lro_advance_dev, a misaligned prev, n + 4 nflows above LVLIP_MAX_BATCH
+ * (the elements are indexed in 32 bits), and with nflows > 0 and either n > 0
+ * or a prev, a NULL or misaligned workspace.  workspace_bytes below
+ * lvlip_lro_advance_carry_workspace_bytes(n, nflows) is LVLIP_ERANGE with
+ * nothing written; LVLIP_ENODEV without a device; a failed launch is LVLIP_EHIP
+ * (lvlip_last_hip_error).
+ * With prev == NULL the call IS lvlip_lro_advance_dev (the same launches with
+ * 2-B lengths, inside the workspace given), so a caller without a carry loses
+ * nothing by calling either form; it still needs this form's workspace size.
+ * Measured: DESIGN.md section 9h. */
+int lvlip_lro_advance_carry_dev(const lvlip_lro_flow *f, uint32_t nflows, const lvlip_lro_rec *rec, uint32_t n,
+                                const lvlip_lro_result *prev, lvlip_lro_result *res,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
+/* Move the receive side on.  For every flow k: d = min(res[k].delivered,
+ * f[k].rcv_wnd); f[k].rcv_nxt += d mod 2^32, f[k].out_off += d, f[k].rcv_wnd -=
+ * d; then res[k].delivered = 0.  sack[], nsack and placed stay: they are the
+ * next lvlip_lro_advance_carry* call's prev.  The call consumes the result, so
+ * applying it twice changes nothing, and lvlip_ack_* or lvlip_rtx* run after it
+ * build the frames they would have built before it (rcv_nxt + delivered is the
+ * same number).  Keys, the plan's order and the disjointness of the flows' out
+ * ranges are preserved: a range only shrinks from its front.
+ * rcv_wnd may reach 0.  Such a flow places nothing more (every data frame is
+ * OUT_OF_WINDOW, a pure ACK NO_DATA) until the caller gives it a fresh region
+ * and plans again; only lvlip_lro_plan refuses a window of 0, the batch calls
+ * take it.
+ * Only f[k] and res[k] are written.  nflows == 0 is a no-op.  LVLIP_EINVAL: NULL
+ * f or res, nflows above LVLIP_LRO_MAX_FLOWS.  _cpu: on the calling thread,
+ * reentrant.  _dev: one launch on the caller's stream, a lane per flow
+ * (asynchronous; no allocation, copy, workspace or synchronisation); f 8-B and
+ * res 16-B aligned device pointers, a misaligned one is LVLIP_EINVAL before any
+ * HIP call; LVLIP_ENODEV without a device; a failed launch is LVLIP_EHIP. */
+int lvlip_lro_next_cpu(lvlip_lro_flow *f, lvlip_lro_result *res, uint32_t nflows);
+int lvlip_lro_next_dev(lvlip_lro_flow *f, lvlip_lro_result *res, uint32_t nflows, void *stream);
+
 /* ---- f1 on the device: the acknowledgement --------------------------------- */
 
 /* What follows the advance step in the reference's receive path is
@@ -597,8 +689,8 @@ int lvlip_ack_dev(const lvlip_ack_tmpl *t, const lvlip_lro_flow *f, const lvlip_
  *             frame that is not fully acknowledged.  A queue entry whose fd.len
  *             is below 54 ends the run.  Only the 54 header bytes are read.
  *   inflight  s[k].nseg - popped
- * The caller carries the state on: snd_una = res.snd_una, seg0 += popped,
- * nseg -= popped.
+ * The state is carried on by lvlip_snd_next_* below (snd_una = res.snd_una,
+ * seg0 += popped, nseg -= popped), or by the caller.
  *
  * Equivalence.  snd_una is monotone in the reference (:330-331 only ever
  * raises it), so the final snd_una and the frames popped are what its
@@ -670,6 +762,27 @@ int lvlip_snd_cpu(const lvlip_lro_flow *f, const lvlip_snd_flow *s, uint32_t nfl
  * one flow it is 0.38 to 0.41 ms. */
 int lvlip_snd_dev(const lvlip_lro_flow *f, const lvlip_snd_flow *s, uint32_t nflows, const lvlip_lro_rec *rec,
                   uint32_t n, const void *base, const lvlip_frame_desc *fd, lvlip_snd_result *res, void *stream);
+
+/* Move the send side on (the receive side's twin is lvlip_lro_next_*).  For
+ * every flow k: p = min(res[k].popped, s[k].nseg); s[k].snd_una =
+ * res[k].snd_una, s[k].seg0 += p, s[k].nseg -= p; then res[k].popped = 0,
+ * res[k].acked = 0 and res[k].inflight = s[k].nseg.  The call consumes the
+ * result, so applying it twice changes nothing, and lvlip_rtx* run after it
+ * re-send the frames they would have re-sent before it (seg0 + popped is the
+ * same entry).  slot0, rtx, win and snd_nxt stay, so the plan's nslots still
+ * holds; the scoreboard is indexed like fd and needs nothing.  res must be one
+ * a lvlip_snd_* call or this call wrote (its snd_una is taken as it is).  A
+ * lvlip_snd_* call with n == 0 leaves res as it was; after this step that is
+ * harmless, because the result is consumed.  Appending new writes to a queue
+ * (snd_nxt, nseg, fresh fd entries) stays with the caller.
+ * Only s[k] and res[k] are written.  nflows == 0 is a no-op.  LVLIP_EINVAL: NULL
+ * s or res, nflows above LVLIP_LRO_MAX_FLOWS.  _cpu: on the calling thread,
+ * reentrant.  _dev: one launch on the caller's stream, a lane per flow
+ * (asynchronous; no allocation, copy, workspace or synchronisation); s 8-B and
+ * res 16-B aligned device pointers, a misaligned one is LVLIP_EINVAL before any
+ * HIP call; LVLIP_ENODEV without a device; a failed launch is LVLIP_EHIP. */
+int lvlip_snd_next_cpu(lvlip_snd_flow *s, lvlip_snd_result *res, uint32_t nflows);
+int lvlip_snd_next_dev(lvlip_snd_flow *s, lvlip_snd_result *res, uint32_t nflows, void *stream);
 
 /* Send the head of the queue again.  Flow k owns the slots s[k].slot0 ..
  * s[k].slot0 + s[k].rtx; nslots is what lvlip_snd_plan returned.  Slot j of

@@ -1,8 +1,10 @@
 /*
  * rcv_cpu.c — TCP receive coalescing (include/lvlip_skb.h, "f1 on the device:
- * receive coalescing"): the plan, the batch on the calling thread, and the
- * advance step.  The device form (rcv_kernels.hip) writes the same records and
- * the same bytes.
+ * receive coalescing"): the plan, the batch on the calling thread, the
+ * advance step, alone and with the islands an earlier batch left, and the step
+ * that moves the flows on to the next batch.  The device forms
+ * (rcv_kernels.hip, adv_kernels.hip, next_kernels.hip) write the same records,
+ * results and bytes.
  *
  * What ip_rcv (src/ip_input.c:17-60), tcp_in / tcp_init_segment
  * (src/tcp.c:36-85), tcp_data_queue (src/tcp_data.c:87-128) and
@@ -155,6 +157,10 @@ int lvlip_lro_cpu(const void *base, const lvlip_frame_desc *fd, uint32_t n, cons
 
 /* --------------------------------------------------------------- advance -- */
 
+/* an interval of a flow's union; bit 63 of hi marks a carried block, which
+ * `placed` does not count */
+#define IVAL_CARRIED (1ull << 63)
+
 typedef struct ival {
     uint32_t flow, lo;
     uint64_t hi;
@@ -168,16 +174,33 @@ static int ival_cmp(const void *a, const void *b)
     return x->hi < y->hi ? -1 : x->hi > y->hi;
 }
 
-int lvlip_lro_advance(const lvlip_lro_flow *f, uint32_t nflows, const lvlip_lro_rec *rec, uint32_t n,
-                      lvlip_lro_result *res)
+/* "Carried blocks" (include/lvlip_skb.h): block j of prev counts for flow f
+ * when l < r <= rcv_wnd, both taken from f's rcv_nxt mod 2^32 */
+static inline int carried_block(const lvlip_lro_flow *f, const lvlip_lro_result *prev, uint32_t j, uint32_t *l,
+                                uint32_t *r)
+{
+    if (j >= prev->nsack) return 0;
+    *l = prev->sack[j].left - f->rcv_nxt;
+    *r = prev->sack[j].right - f->rcv_nxt;
+    return *l < *r && *r <= f->rcv_wnd;
+}
+
+/* lvlip_lro_advance (prev NULL) and lvlip_lro_advance_carry.  prev may be res:
+ * every interval is taken before res is zeroed. */
+static int advance(const lvlip_lro_flow *f, uint32_t nflows, const lvlip_lro_rec *rec, uint32_t n,
+                   const lvlip_lro_result *prev, lvlip_lro_result *res)
 {
     if ((nflows && (!f || !res)) || (n && !rec)) return LVLIP_EINVAL;
-    if (nflows) memset(res, 0, (size_t)nflows * sizeof *res);
     size_t m = 0;
+    uint32_t l, r;
     for (uint32_t i = 0; i < n; i++) m += rec[i].status == LVLIP_LRO_PLACED && rec[i].flow < nflows;
-    if (m == 0) return LVLIP_OK;
-    ival *v = malloc(m * sizeof *v);
-    if (!v) return LVLIP_ENOMEM;
+    for (uint32_t k = 0; prev && k < nflows; k++)
+        for (uint32_t j = 0; j < 4u; j++) m += (size_t)carried_block(&f[k], &prev[k], j, &l, &r);
+    ival *v = NULL;
+    if (m) {
+        v = malloc(m * sizeof *v);
+        if (!v) return LVLIP_ENOMEM;
+    }
     m = 0;
     for (uint32_t i = 0; i < n; i++) {
         if (rec[i].status != LVLIP_LRO_PLACED || rec[i].flow >= nflows) continue;
@@ -186,30 +209,68 @@ int lvlip_lro_advance(const lvlip_lro_flow *f, uint32_t nflows, const lvlip_lro_
         v[m].hi = (uint64_t)rec[i].rel + rec[i].dlen;
         m++;
     }
+    for (uint32_t k = 0; prev && k < nflows; k++)
+        for (uint32_t j = 0; j < 4u; j++) {
+            if (!carried_block(&f[k], &prev[k], j, &l, &r)) continue;
+            v[m].flow = k;
+            v[m].lo = l;
+            v[m].hi = r | IVAL_CARRIED;
+            m++;
+        }
+    if (nflows) memset(res, 0, (size_t)nflows * sizeof *res);
+    if (m == 0) return LVLIP_OK;
     qsort(v, m, sizeof *v, ival_cmp);
     for (size_t a = 0; a < m;) {
-        lvlip_lro_result *r = &res[v[a].flow];
+        lvlip_lro_result *o = &res[v[a].flow];
         const uint32_t rcv_nxt = f[v[a].flow].rcv_nxt;
         size_t b = a;
         while (b < m && v[b].flow == v[a].flow) {
             /* one island: everything that touches or overlaps [lo, hi) */
             const uint64_t lo = v[b].lo;
-            uint64_t hi = v[b].hi;
-            r->placed++;
+            uint64_t hi = v[b].hi & ~IVAL_CARRIED;
+            o->placed += !(v[b].hi & IVAL_CARRIED);
             for (b++; b < m && v[b].flow == v[a].flow && v[b].lo <= hi; b++) {
-                if (v[b].hi > hi) hi = v[b].hi;
-                r->placed++;
+                if ((v[b].hi & ~IVAL_CARRIED) > hi) hi = v[b].hi & ~IVAL_CARRIED;
+                o->placed += !(v[b].hi & IVAL_CARRIED);
             }
             if (lo == 0) {
-                r->delivered = (uint32_t)hi; /* <= rcv_wnd <= 2^30 */
-            } else if (r->nsack < 4u) {
-                r->sack[r->nsack].left = rcv_nxt + (uint32_t)lo;
-                r->sack[r->nsack].right = rcv_nxt + (uint32_t)hi;
-                r->nsack++;
+                o->delivered = (uint32_t)hi; /* <= rcv_wnd <= 2^30 */
+            } else if (o->nsack < 4u) {
+                o->sack[o->nsack].left = rcv_nxt + (uint32_t)lo;
+                o->sack[o->nsack].right = rcv_nxt + (uint32_t)hi;
+                o->nsack++;
             }
         }
         a = b;
     }
     free(v);
+    return LVLIP_OK;
+}
+
+int lvlip_lro_advance(const lvlip_lro_flow *f, uint32_t nflows, const lvlip_lro_rec *rec, uint32_t n,
+                      lvlip_lro_result *res)
+{
+    return advance(f, nflows, rec, n, NULL, res);
+}
+
+int lvlip_lro_advance_carry(const lvlip_lro_flow *f, uint32_t nflows, const lvlip_lro_rec *rec, uint32_t n,
+                            const lvlip_lro_result *prev, lvlip_lro_result *res)
+{
+    return advance(f, nflows, rec, n, prev, res);
+}
+
+/* ------------------------------------------------------------------ next -- */
+
+int lvlip_lro_next_cpu(lvlip_lro_flow *f, lvlip_lro_result *res, uint32_t nflows)
+{
+    if (nflows == 0) return LVLIP_OK;
+    if (!f || !res || nflows > LVLIP_LRO_MAX_FLOWS) return LVLIP_EINVAL;
+    for (uint32_t k = 0; k < nflows; k++) {
+        const uint32_t d = res[k].delivered < f[k].rcv_wnd ? res[k].delivered : f[k].rcv_wnd;
+        f[k].rcv_nxt += d;
+        f[k].out_off += d;
+        f[k].rcv_wnd -= d;
+        res[k].delivered = 0;
+    }
     return LVLIP_OK;
 }

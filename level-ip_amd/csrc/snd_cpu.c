@@ -172,3 +172,21 @@ int lvlip_rtx_sack_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, con
     }
     return LVLIP_OK;
 }
+
+/* ------------------------------------------------------------------ next -- */
+
+int lvlip_snd_next_cpu(lvlip_snd_flow *s, lvlip_snd_result *res, uint32_t nflows)
+{
+    if (nflows == 0) return LVLIP_OK;
+    if (!s || !res || nflows > LVLIP_LRO_MAX_FLOWS) return LVLIP_EINVAL;
+    for (uint32_t k = 0; k < nflows; k++) {
+        const uint32_t p = res[k].popped < s[k].nseg ? res[k].popped : s[k].nseg;
+        s[k].snd_una = res[k].snd_una;
+        s[k].seg0 += p;
+        s[k].nseg -= p;
+        res[k].popped = 0;
+        res[k].acked = 0;
+        res[k].inflight = s[k].nseg;
+    }
+    return LVLIP_OK;
+}

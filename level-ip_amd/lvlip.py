@@ -230,6 +230,12 @@ SIGNATURES = {
     "lvlip_lro_advance": (_INT, [_P, _U32, _P, _U32, _P]),
     "lvlip_lro_advance_workspace_bytes": (_SZ, [_U32, _U32]),
     "lvlip_lro_advance_dev": (_INT, [_P, _U32, _P, _U32, _P, _P, _SZ, _P]),
+    # f1 on the device: state across batches (rcv_cpu.c, adv_kernels.hip, next_kernels.hip)
+    "lvlip_lro_advance_carry": (_INT, [_P, _U32, _P, _U32, _P, _P]),
+    "lvlip_lro_advance_carry_workspace_bytes": (_SZ, [_U32, _U32]),
+    "lvlip_lro_advance_carry_dev": (_INT, [_P, _U32, _P, _U32, _P, _P, _P, _SZ, _P]),
+    "lvlip_lro_next_cpu": (_INT, [_P, _P, _U32]),
+    "lvlip_lro_next_dev": (_INT, [_P, _P, _U32, _P]),
     # f1 on the device: the acknowledgement (ack_cpu.c, ack_kernels.hip)
     "lvlip_ack_plan": (_U32, [_P, _P, _U32, _PU64]),
     "lvlip_ack_cpu": (_INT, [_P, _P, _P, _U32, _U32, _P, _P]),
@@ -240,6 +246,8 @@ SIGNATURES = {
     "lvlip_snd_dev": (_INT, [_P, _P, _U32, _P, _U32, _P, _P, _P, _P]),
     "lvlip_rtx_cpu": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P]),
     "lvlip_rtx_dev": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P]),
+    "lvlip_snd_next_cpu": (_INT, [_P, _P, _U32]),
+    "lvlip_snd_next_dev": (_INT, [_P, _P, _U32, _P]),
     # f2 on the device: the scoreboard and the selective retransmit (sack_cpu.c, sack_kernels.hip, snd_*)
     "lvlip_sack_workspace_bytes": (_SZ, [_U32, _U32]),
     "lvlip_sack_cpu": (_INT, [_P, _P, _U32, _P, _P, _P, _U32, _P, _P, _P, _P]),
@@ -803,6 +811,88 @@ def lro_advance_dev(flows_t, rec_t, res_t=None, workspace_t=None, stream=None):
     return res_t[:LRO_RESULT_DTYPE.itemsize * nflows]
 
 
+# ------------------------------------- f1 on the device: state across batches --
+
+def lro_advance_carry(flows: np.ndarray, rec: np.ndarray, prev: Optional[np.ndarray] = None,
+                      res: Optional[np.ndarray] = None) -> np.ndarray:
+    """lvlip_lro_advance_carry: lro_advance over the records and the islands
+    `prev` (LRO_RESULT_DTYPE per flow, or None) carries from an earlier batch.
+    Returns the LRO_RESULT_DTYPE array: `res` when given (it may be `prev`: in
+    place), else a new one."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    rec = np.ascontiguousarray(rec, dtype=LRO_REC_DTYPE)
+    if prev is not None:
+        _planned(prev, LRO_RESULT_DTYPE, "prev: a contiguous LRO_RESULT_DTYPE array", writeable=False)
+    if res is None:
+        res = np.zeros(flows.size, dtype=LRO_RESULT_DTYPE)
+    _planned(res, LRO_RESULT_DTYPE, "res: a writeable contiguous LRO_RESULT_DTYPE array")
+    if any(r is not None and r.size != flows.size for r in (prev, res)):
+        raise ValueError("one result per flow")
+    _check(_lib.lvlip_lro_advance_carry(_aptr(flows), flows.size, _aptr(rec), rec.size, _aptr(prev), _aptr(res)),
+           "lvlip_lro_advance_carry")
+    return res
+
+
+def lro_advance_carry_workspace_bytes(n: int, nflows: int) -> int:
+    """lvlip_lro_advance_carry_workspace_bytes: the device workspace
+    lro_advance_carry_dev needs for n records and nflows flows (not 0 for
+    n == 0; 0 without a flow, and without a device)."""
+    return int(_lib.lvlip_lro_advance_carry_workspace_bytes(n, nflows))
+
+
+def lro_advance_carry_dev(flows_t, rec_t, prev_t=None, res_t=None, workspace_t=None, stream=None):
+    """lvlip_lro_advance_carry_dev on CUDA uint8 tensors: lro_advance_dev's
+    arguments and prev_t, 48 bytes per flow (the results of an earlier batch;
+    None for no carry; it may be res_t).  Returns res_t, 48 bytes per flow (a
+    new tensor unless given).  workspace_t (a new tensor unless given) holds at
+    least lro_advance_carry_workspace_bytes(n, nflows) bytes at a 256-B aligned
+    address.  Asynchronous on `stream` (default: current)."""
+    import torch
+
+    n = _records(rec_t, 16)
+    nflows = _records(flows_t, LRO_FLOW_DTYPE.itemsize)
+    device = flows_t.device if flows_t is not None else rec_t.device
+    _need(prev_t, "prev_t", LRO_RESULT_DTYPE.itemsize, nflows, "flow", optional=True)
+    res_t = _result(res_t, "res_t", LRO_RESULT_DTYPE.itemsize, nflows, "flow", device)
+    need = lro_advance_carry_workspace_bytes(n, nflows) if nflows and (n or prev_t is not None) else 0
+    if workspace_t is None and need:
+        workspace_t = torch.empty(need, dtype=torch.uint8, device=device)
+    s = _stream(stream, device)
+    _check(_lib.lvlip_lro_advance_carry_dev(_tptr(flows_t, nflows), nflows, _tptr(rec_t, n), n, _tptr(prev_t, nflows),
+                                            res_t.data_ptr(), _tptr(workspace_t), _records(workspace_t, 1),
+                                            s.cuda_stream), "lvlip_lro_advance_carry_dev")
+    return res_t[:LRO_RESULT_DTYPE.itemsize * nflows]
+
+
+def _next_cpu(fn, what: str, flows: np.ndarray, dtype, res: np.ndarray, res_dtype) -> None:
+    _planned(flows, dtype, f"{what}: the flows as a writeable contiguous array of their dtype")
+    _planned(res, res_dtype, f"{what}: the results as a writeable contiguous array of their dtype")
+    if res.size != flows.size:
+        raise ValueError("one result per flow")
+    _check(fn(_aptr(flows), _aptr(res), flows.size), what)
+
+
+def _next_dev(fn, what: str, flows_t, per: int, res_t, res_per: int, stream) -> None:
+    nflows = _nbytes(flows_t) // per
+    _need(res_t, "res_t", res_per, nflows, "flow")
+    s = _stream(stream, flows_t.device)
+    _check(fn(_tptr(flows_t, nflows), _tptr(res_t, nflows), nflows, s.cuda_stream), what)
+
+
+def lro_next_cpu(flows: np.ndarray, res: np.ndarray) -> None:
+    """lvlip_lro_next_cpu: moves the planned flows on by res["delivered"], IN
+    PLACE (rcv_nxt, out_off, rcv_wnd), and zeroes res["delivered"]; what is
+    left of res is the next lro_advance_carry's prev."""
+    _next_cpu(_lib.lvlip_lro_next_cpu, "lvlip_lro_next_cpu", flows, LRO_FLOW_DTYPE, res, LRO_RESULT_DTYPE)
+
+
+def lro_next_dev(flows_t, res_t, stream=None) -> None:
+    """lvlip_lro_next_dev on CUDA uint8 tensors (48 bytes per flow each), both
+    updated in place.  One launch on `stream` (default: current), asynchronous."""
+    _next_dev(_lib.lvlip_lro_next_dev, "lvlip_lro_next_dev", flows_t, LRO_FLOW_DTYPE.itemsize, res_t,
+              LRO_RESULT_DTYPE.itemsize, stream)
+
+
 # ------------------------------------- f1 on the device: the acknowledgement --
 
 # struct lvlip_ack_tmpl (include/lvlip_skb.h), 64 B
@@ -931,6 +1021,20 @@ def snd_dev(flows_t, snd_t, rec_t, base_t, fd_t, res_t=None, stream=None):
     _check(_lib.lvlip_snd_dev(flows_t.data_ptr(), snd_t.data_ptr(), nflows, _tptr(rec_t, n), n, base_t.data_ptr(),
                               fd_t.data_ptr(), res_t.data_ptr(), s.cuda_stream), "lvlip_snd_dev")
     return res_t[:SND_RESULT_DTYPE.itemsize * nflows]
+
+
+def snd_next_cpu(snd: np.ndarray, res: np.ndarray) -> None:
+    """lvlip_snd_next_cpu: moves the planned send sides on by res["popped"],
+    IN PLACE (snd_una, seg0, nseg), and consumes res (popped, acked 0; inflight
+    the queue's length)."""
+    _next_cpu(_lib.lvlip_snd_next_cpu, "lvlip_snd_next_cpu", snd, SND_FLOW_DTYPE, res, SND_RESULT_DTYPE)
+
+
+def snd_next_dev(snd_t, res_t, stream=None) -> None:
+    """lvlip_snd_next_dev on CUDA uint8 tensors (32 bytes per flow each), both
+    updated in place.  One launch on `stream` (default: current), asynchronous."""
+    _next_dev(_lib.lvlip_snd_next_dev, "lvlip_snd_next_dev", snd_t, SND_FLOW_DTYPE.itemsize, res_t,
+              SND_RESULT_DTYPE.itemsize, stream)
 
 
 def _rtx_cpu(flows, lro_res, snd, snd_res, sacked, base, fdescs, selective: bool):
