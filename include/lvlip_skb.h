@@ -774,7 +774,8 @@ int lvlip_snd_dev(const lvlip_lro_flow *f, const lvlip_snd_flow *s, uint32_t nfl
  * a lvlip_snd_* call or this call wrote (its snd_una is taken as it is).  A
  * lvlip_snd_* call with n == 0 leaves res as it was; after this step that is
  * harmless, because the result is consumed.  Appending new writes to a queue
- * (snd_nxt, nseg, fresh fd entries) stays with the caller.
+ * (snd_nxt, nseg, fresh fd entries) and giving popped entries back is
+ * lvlip_push_* below ("the write queue").
  * Only s[k] and res[k] are written.  nflows == 0 is a no-op.  LVLIP_EINVAL: NULL
  * s or res, nflows above LVLIP_LRO_MAX_FLOWS.  _cpu: on the calling thread,
  * reentrant.  _dev: one launch on the caller's stream, a lane per flow
@@ -986,6 +987,128 @@ int lvlip_rtx_sack_dev(const lvlip_lro_flow *f, const lvlip_lro_result *lro, con
                        const lvlip_snd_result *snd, const uint8_t *sacked, uint32_t nflows, uint32_t nslots,
                        void *base, const lvlip_frame_desc *fd, lvlip_frame_desc *fd_out, uint32_t *pick,
                        void *stream);
+
+/* ---- f2 on the device: the write queue -------------------------------------- */
+
+/* tcp_send + tcp_queue_transmit_skb (src/tcp_output.c:131-156, 445-478) per
+ * round: bytes the application has made ready are cut into segments, built as
+ * frames in the flow's slots of the TX ring and appended to its write queue,
+ * and the entries lvlip_snd_next_* popped are given back.  A connection that
+ * keeps writing then needs a ring and an fd region of `cap` slots, not of
+ * everything it will ever send, and no host step per write: the loop is
+ * ... -> lvlip_snd_next_* -> lvlip_push_* -> lvlip_rtx_sack_* -> ...
+ *
+ * lvlip_push_flow k is the write side of flow k of the reverse plan, as
+ * lvlip_snd_flow k is.  Its frame slot j (0 <= j < cap) is the stride bytes at
+ * ring_off + j*stride of the ring; its fd / scoreboard region is the indices
+ * [q0, q0 + cap).  Slots are filled round robin from slot_nxt.
+ *
+ * One call does for flow k, from the values at entry:
+ *   1 compact  if s[k].seg0 != q0: fd[q0 + i] = fd[seg0 + i] for i < nseg, and
+ *              likewise sacked[], as memmove does (entries that are not
+ *              overwritten keep their bytes); seg0 = q0, res.moved = nseg
+ *              (else 0).  Frames do not move: fd holds their offsets.
+ *   2 count    span = (snd_nxt - snd_una) mod 2^32; m is the largest count with
+ *              m <= cap - nseg, m <= push, m <= ceil(unsent / mss) and
+ *              span + min(m*mss, unsent) <= wnd.  Only whole segments are
+ *              pushed; a short one is only the one that ends `unsent`.
+ *   3 build    segment i < m carries dlen_i = min(mss, unsent - i*mss) bytes; its
+ *              frame, at ring_off + ((slot_nxt + i) mod cap)*stride, holds
+ *              exactly the bytes lvlip_tso_* writes for segment i of a send
+ *              {payload_off = pay_off, len = unsent, mss, hdr} whose template
+ *              has seq = htonl(snd_nxt), ack_seq = htonl(f[k].rcv_nxt +
+ *              lro[k].delivered) and window = htons(s[k].win) in place of its
+ *              own (lvlip_rtx_*'s two fields, src/tcp_output.c:107-109); PSH
+ *              thus goes only on the segment that empties `unsent` (:466).
+ *              fd[q0 + nseg + i] = fd_out[slot0 + i] = {offset, 54 + dlen_i, 0}
+ *              and sacked[q0 + nseg + i] = 0.  Slots i >= m of the flow's
+ *              `push` get fd_out = {0, 0, 0}.  No byte of the ring outside the
+ *              m frames is stored: stride gaps keep their bytes.
+ *   4 step     nseg += m, snd_nxt += bytes, pay_off += bytes, unsent -= bytes,
+ *              slot_nxt = (slot_nxt + m) mod cap; res[k] = {m, bytes, q0 + nseg
+ *              (the first new entry's fd index), moved}.
+ *
+ * Contract.  The call runs after lvlip_snd_next_* has consumed the last
+ * lvlip_snd_result; it ignores `popped`.  The queue's entries hold the cap
+ * slots first in, first out, starting from an empty queue (every entry of a
+ * queue was appended by these calls), so a slot being filled never holds a
+ * live frame.  `pick` values of an earlier lvlip_rtx_sack_* call are stale
+ * after a compaction.  Refilling pay_off / unsent / wnd is the application's
+ * step, as reopening rcv_wnd is.  wnd is the hook for a peer's or a congestion
+ * window: the reference never limits the bytes in flight (snd_wnd is written
+ * once, src/tcp_output.c:429); 2^30 means "no limit".  A FIN would have to
+ * advance snd_nxt: that stays with the caller, and the plan refuses it. */
+typedef struct lvlip_push_flow {      /* one per planned flow; sizeof == 112 */
+    uint64_t pay_off;                 /* the next unsent byte, from the payload base; any alignment */
+    uint64_t ring_off;                /* frame slot 0, from the ring base; any alignment */
+    uint32_t unsent;                  /* bytes ready to send, 0 .. 2^30 */
+    uint32_t stride;                  /* >= 54 + mss; any value */
+    uint32_t cap;                     /* frame slots = fd entries of the flow, > 0 */
+    uint32_t q0;                      /* the flow's fd / scoreboard region is [q0, q0 + cap) */
+    uint32_t slot_nxt;                /* the next frame slot to fill, < cap */
+    uint32_t push;                    /* the most segments one call may append */
+    uint32_t slot0;                   /* filled by the plan: the running sum of push */
+    uint32_t wnd;                     /* bytes allowed between snd_una and snd_nxt, 0 .. 2^30 */
+    uint16_t mss;                     /* 1 .. 65495 */
+    uint16_t reserved;                /* 0 */
+    uint8_t  hdr[54];                 /* as lvlip_tso_send.hdr; seq, ack_seq and window are ignored */
+    uint8_t  pad[6];                  /* 0 */
+} lvlip_push_flow;
+
+typedef struct lvlip_push_result {    /* one per planned flow; sizeof == 16 */
+    uint32_t pushed;                  /* m */
+    uint32_t bytes;                   /* payload bytes of the m segments */
+    uint32_t first;                   /* the fd index of the first new entry */
+    uint32_t moved;                   /* queue entries moved down to q0 */
+} lvlip_push_result;
+
+/* Host only: validates the write sides against the send sides and fills slot0
+ * with the running sum of push; nothing else is modified.  Returns the total
+ * slot count (nslots of lvlip_push_*), or 0xFFFFFFFF with w unwritten for: a
+ * template lvlip_tso_plan refuses, or one with FIN, SYN, RST or URG set; cap 0,
+ * slot_nxt >= cap, mss 0 or above 65495, stride < 54 + mss, unsent or wnd above
+ * 2^30, nonzero reserved or pad; a region [q0, q0 + cap) that passes 2^32 or a
+ * ring range that passes 2^64; two flows whose [q0, q0 + cap) overlap, or whose
+ * [ring_off, ring_off + cap*stride) overlap; a non-empty queue of s[k] that is
+ * not inside [q0, q0 + cap); a total of push or of cap above LVLIP_MAX_BATCH;
+ * nflows above LVLIP_LRO_MAX_FLOWS; NULL w or s; or no memory for the overlap
+ * checks.  *ring_bytes (may be NULL) gets the largest ring_off + (cap - 1)*stride
+ * + 54 + mss, the bytes the ring must hold, and *nfd (may be NULL) the largest
+ * q0 + cap, the entries fd, sacked and the scoreboard calls' arrays must hold. */
+uint32_t lvlip_push_plan(lvlip_push_flow *w, const lvlip_snd_flow *s, uint32_t nflows, uint64_t *ring_bytes,
+                         uint32_t *nfd);
+
+/* On the calling thread, one checksum() per field (seg_cpu.c's frame writer, so
+ * the frames are lvlip_tso_cpu's by construction).  f, lro (may be NULL:
+ * delivered 0) and s exactly as lvlip_rtx_* takes them; payload is only read;
+ * base is the ring; sacked may be NULL; s, w, fd, sacked, fd_out and res are
+ * written.  nslots is what lvlip_push_plan returned.  Returns 0, or
+ * LVLIP_EINVAL with nothing written: NULL f, s, w, fd or res with nflows > 0;
+ * NULL payload, base or fd_out, or nflows 0, with nslots > 0; nflows above
+ * LVLIP_LRO_MAX_FLOWS, nslots above LVLIP_MAX_BATCH; w not as the plan left it
+ * (slot0, nslots) or a flow the plan would refuse for its own fields or its
+ * queue.  nflows == 0 is a no-op; with nslots == 0 the call still compacts and
+ * writes res.  Reentrant. */
+int lvlip_push_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, lvlip_snd_flow *s, lvlip_push_flow *w,
+                   uint32_t nflows, uint32_t nslots, const void *payload, void *base, lvlip_frame_desc *fd,
+                   uint8_t *sacked, lvlip_frame_desc *fd_out, lvlip_push_result *res);
+
+/* The same bytes of every output on the caller's stream (asynchronous; no
+ * allocation, copy, atomics or synchronisation, no workspace beyond res), in
+ * three launches: a wave per flow moves the queue down in ascending chunks of
+ * 64 entries, each read completely before it is written, and one lane counts m
+ * and writes res; lvlip_tso_dev's kernel body, a 16-lane row per slot, builds
+ * the frames of the live slots (payload copy and TCP checksum in one pass); a
+ * lane per flow does the step.  All pointers are device pointers: f, s and w
+ * 8-B aligned, lro, fd, fd_out and res 16-B aligned, payload, base and sacked
+ * any alignment.  The NULL and limit refusals of lvlip_push_cpu and a
+ * misaligned pointer are LVLIP_EINVAL before any HIP call; LVLIP_ENODEV without
+ * a device; a failed launch is LVLIP_EHIP (lvlip_last_hip_error).  The device
+ * does not validate w again: the caller planned it.  Measured: DESIGN.md
+ * section 9i. */
+int lvlip_push_dev(const lvlip_lro_flow *f, const lvlip_lro_result *lro, lvlip_snd_flow *s, lvlip_push_flow *w,
+                   uint32_t nflows, uint32_t nslots, const void *payload, void *base, lvlip_frame_desc *fd,
+                   uint8_t *sacked, lvlip_frame_desc *fd_out, lvlip_push_result *res, void *stream);
 
 /* RFC 1071 pseudo-header seed with the carries folded back (for RX verify of
  * checksums produced by RFC-correct peers). */

@@ -10,8 +10,7 @@
 #include "tcp_hdr.h"
 
 #define TSO_HDR TCP_FRAME_HDR
-#define TSO_MSS_MAX 65495u /* 65535 - 40: the IPv4 total length is 16 bits */
-#define TCP_FIN_PSH 0x09u  /* byte 13 of the TCP header: FIN 0x01, PSH 0x08 */
+#define TSO_MSS_MAX TCP_MSS_MAX
 
 static int send_ok(const lvlip_tso_send *s)
 {
@@ -77,16 +76,8 @@ int lvlip_tso_cpu(const void *payload, const lvlip_tso_send *s, uint32_t n, void
             const uint64_t done = i * t->mss;
             const uint32_t dlen = t->len - done < t->mss ? (uint32_t)(t->len - done) : t->mss;
             const uint64_t off = t->out_off + i * t->stride;
-            uint8_t *f = (uint8_t *)out + off;
-            uint8_t *ih = f + 14, *th = f + 34;
-            memcpy(f, t->hdr, TSO_HDR);
-            memcpy(f + TSO_HDR, src + done, dlen);
-            ip_output_tail(ih, 40u + dlen);
-            /* tcp_transmit_skb: seq (src/tcp_output.c:106); PSH on the last
-             * segment only (src/tcp_output.c:466), and FIN with it */
-            put_be32(th + 4, seq0 + (uint32_t)done);
-            if (i + 1u != k) th[13] &= (uint8_t)~TCP_FIN_PSH;
-            tcp_csum_tail(ih, th, 20u + dlen);
+            /* PSH on the last segment only (src/tcp_output.c:466), and FIN with it */
+            tcp_seg_write((uint8_t *)out + off, t->hdr, src + done, dlen, seq0 + (uint32_t)done, i + 1u == k);
             if (fd) {
                 lvlip_frame_desc *d = &fd[t->seg0 + i];
                 d->offset = off;

@@ -46,17 +46,12 @@
 
 #include <stdint.h>
 
-#include "csum_dev.h"
-#include "row_copy.h"
-#include "tcp_hdr_dev.h"
+#include "seg_frame_dev.h"
 
 namespace lvlip {
 
-constexpr uint32_t TSO_ROW = 16;                 // lanes per segment
-constexpr uint32_t TSO_SEGS = 256 / TSO_ROW;     // segments per workgroup
-constexpr int TSO_U = 4;                         // sweeps of a row in flight
-constexpr int TSO_HDR = TCP_FRAME_HDR;
-
+// the row's work itself is tso_frame (seg_frame_dev.h), which k_push
+// (push_kernels.hip) runs too; this kernel maps segments to sends
 __global__ __launch_bounds__(256) void k_tso(const uint8_t* payload, const lvlip_tso_send* s, uint32_t n,
                                              uint32_t nseg, uint8_t* out, lvlip_frame_desc* fd) {
     const uint32_t tl = threadIdx.x & (TSO_ROW - 1u);
@@ -84,58 +79,10 @@ __global__ __launch_bounds__(256) void k_tso(const uint8_t* payload, const lvlip
     const uint64_t off = t->out_off + (uint64_t)i * t->stride;
     const uint64_t F = reinterpret_cast<uint64_t>(out) + off;      // the frame's first byte
     const uint64_t S = reinterpret_cast<uint64_t>(payload) + t->payload_off + done;
-    const int f = (int)(F & 15ull);
-    const uint64_t D = F - (uint64_t)f;                            // destination chunk 0
-    const int L = TSO_HDR + (int)dlen;
-    const uint32_t nch = live ? (uint32_t)(f + L + 15) >> 4 : 0u;  // chunks the frame touches
-    const uint32_t hk = (uint32_t)(f + TSO_HDR + 15) >> 4;         // of them with header bytes: 4 or 5
-    const uint32_t sel = (F & 1ull) ? 0x02030001u : 0x03020100u;
-
-    // ---- payload: copy and sum, destination chunk by destination chunk
-    uint32_t acc = 0;
-    uint4 keep = make_uint4(0u, 0u, 0u, 0u);  // the payload bytes of this lane's header chunk
-    for (uint32_t k0 = 0; k0 < nch; k0 += TSO_ROW * TSO_U) {
-        // chunk k's byte j is payload byte 16 k - f - 54 + j of the segment
-        uint4 v[TSO_U];
-        row_gather<TSO_U, true>(S, f + TSO_HDR, dlen, nch, k0, tl, v);
-#pragma unroll
-        for (int u = 0; u < TSO_U; ++u) {
-            const uint32_t k = k0 + (uint32_t)u * TSO_ROW + tl;
-            acc = chunk_acc(v[u], sel, acc);
-            if (k < nch) {
-                if (k >= hk) store_chunk(D + 16ull * k, v[u], 0, min(16, f + L - (int)(16u * k)));
-                else keep = v[u];  // k = tl < hk <= 5: the first round's first sweep
-            }
-        }
-    }
-    const uint32_t W = row_sum_dpp(acc);  // the payload's word sum, in every lane of the row
-
-    // ---- the 54 header bytes (every lane of the row the same)
-    h[13] &= 0xffffu;                                             // bytes 52-53; the rest is the struct's pad
-    h[4] = (h[4] & 0xffff0000u) | bswap16u(40u + dlen);         // ip.len, src/ip_output.c:35,46
-    h[6] &= 0xffff0000u;                                          // ip.csum = 0, src/ip_output.c:42
-    const uint32_t ipw = (h[3] >> 16) + halves(h[4]) + halves(h[5]) + halves(h[6]) + halves(h[7]) +
-                         (h[8] & 0xffffu);
-    h[6] |= (uint32_t)finish(0u, ipw);                            // ip_send_check, src/ip_output.c:8-12
     const uint32_t seq0 = __builtin_bswap32((h[9] >> 16) | (h[10] << 16));
-    const uint32_t seq = __builtin_bswap32(seq0 + (uint32_t)done);  // src/tcp_output.c:106,121
-    h[9] = (h[9] & 0xffffu) | (seq << 16);
-    h[10] = (h[10] & 0xffff0000u) | (seq >> 16);
-    if (!last) h[11] &= ~(0x09u << 24);                           // FIN, PSH: the last segment's
-    h[12] &= 0xffffu;                                             // tcp.csum = 0, src/tcp_output.c:110
-    const uint32_t thw = hdr_tcp_words(h);
-    h[12] |= (uint32_t)finish(hdr_tcp_seed(h, 20u + dlen), thw + W) << 16;  // src/tcp_output.c:126
-
-    // ---- the chunks with header bytes, merged with the payload bytes kept back
-    if (tl < hk && tl < nch) {
-        const uint4 blk[4] = {make_uint4(h[0], h[1], h[2], h[3]), make_uint4(h[4], h[5], h[6], h[7]),
-                              make_uint4(h[8], h[9], h[10], h[11]), make_uint4(h[12], h[13], 0u, 0u)};
-        const uint4 hv = hdr_chunk(tl, f, blk);
-        const uint4 v = make_uint4(keep.x | hv.x, keep.y | hv.y, keep.z | hv.z, keep.w | hv.w);
-        store_chunk(D + 16ull * tl, v, tl == 0u ? f : 0, min(16, f + L - (int)(16u * tl)));
-    }
+    tso_frame(tl, live, h, F, S, dlen, last, [=](uint32_t(&)[14]) { return seq0 + (uint32_t)done; });
     if (fd && live && tl == 0u)
-        store_global(reinterpret_cast<uint64_t>(fd + g), u32x4{(uint32_t)off, (uint32_t)(off >> 32), (uint32_t)L, 0u});
+        store_global(reinterpret_cast<uint64_t>(fd + g), u32x4{(uint32_t)off, (uint32_t)(off >> 32), (uint32_t)TSO_HDR + dlen, 0u});
 }
 
 }  // namespace lvlip

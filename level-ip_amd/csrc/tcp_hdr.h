@@ -74,6 +74,26 @@ static inline void tcp_csum_tail(const uint8_t *ih, uint8_t *th, uint32_t l4)
     memcpy(th + 16, &tc, 2);
 }
 
+#define TCP_MSS_MAX 65495u /* 65535 - 40: the IPv4 total length is 16 bits */
+#define TCP_FIN_PSH 0x09u  /* byte 13 of the TCP header: FIN 0x01, PSH 0x08 */
+
+/* One segment of tcp_send at f (src/tcp_output.c:445-478 -> tcp_transmit_skb,
+ * :93-129 -> ip_output, src/ip_output.c:14-56): the template's 54 bytes, dlen
+ * payload bytes from src, the IP length and checksum, seq (:106), PSH and FIN
+ * on the last segment only (:466), the TCP checksum.  The one frame writer of
+ * lvlip_tso_cpu and lvlip_push_cpu. */
+static inline void tcp_seg_write(uint8_t *f, const uint8_t *hdr, const uint8_t *src, uint32_t dlen, uint32_t seq,
+                                 int last)
+{
+    uint8_t *ih = f + 14, *th = f + 34;
+    memcpy(f, hdr, TCP_FRAME_HDR);
+    memcpy(f + TCP_FRAME_HDR, src, dlen);
+    ip_output_tail(ih, 40u + dlen);
+    put_be32(th + 4, seq);
+    if (!last) th[13] &= (uint8_t)~TCP_FIN_PSH;
+    tcp_csum_tail(ih, th, 20u + dlen);
+}
+
 static inline int range_cmp(const void *a, const void *b)
 {
     const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;

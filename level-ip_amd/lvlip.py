@@ -254,6 +254,10 @@ SIGNATURES = {
     "lvlip_sack_dev": (_INT, [_P, _P, _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _P, _SZ, _P]),
     "lvlip_rtx_sack_cpu": (_INT, [_P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P]),
     "lvlip_rtx_sack_dev": (_INT, [_P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P]),
+    # f2 on the device: the write queue (push_cpu.c, push_kernels.hip)
+    "lvlip_push_plan": (_U32, [_P, _P, _U32, _PU64, _PU32]),
+    "lvlip_push_cpu": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P]),
+    "lvlip_push_dev": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "lvlip_auto_kernel": (_INT, [_I32, _U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (_U32, [_U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (_STR, []),
@@ -1194,6 +1198,106 @@ def rtx_sack_dev(flows_t, lro_res_t, snd_t, snd_res_t, sacked_t, nslots: int, ba
     (default: current)."""
     return _rtx_dev(flows_t, lro_res_t, snd_t, snd_res_t, sacked_t, nslots, base_t, fd_t, fd_out_t, pick_t, stream,
                     True)
+
+
+# ------------------------------------------- f2 on the device: the write queue --
+
+# struct lvlip_push_flow (112 B) / lvlip_push_result (16 B), include/lvlip_skb.h
+PUSH_FLOW_DTYPE = np.dtype([("pay_off", "<u8"), ("ring_off", "<u8"), ("unsent", "<u4"), ("stride", "<u4"),
+                            ("cap", "<u4"), ("q0", "<u4"), ("slot_nxt", "<u4"), ("push", "<u4"), ("slot0", "<u4"),
+                            ("wnd", "<u4"), ("mss", "<u2"), ("reserved", "<u2"), ("hdr", "u1", (54,)),
+                            ("pad", "u1", (6,))])
+PUSH_RESULT_DTYPE = np.dtype([("pushed", "<u4"), ("bytes", "<u4"), ("first", "<u4"), ("moved", "<u4")])
+PUSH_NO_LIMIT = 0x40000000
+assert PUSH_FLOW_DTYPE.itemsize == 112 and PUSH_RESULT_DTYPE.itemsize == 16
+
+
+def push_flow(hdr, pay_off: int, unsent: int, mss: int, ring_off: int, cap: int, q0: int, push: int,
+              stride: int = 0, wnd: int = PUSH_NO_LIMIT, slot_nxt: int = 0) -> np.ndarray:
+    """One lvlip_push_flow (a 1-element PUSH_FLOW_DTYPE array); stride 0 means
+    54 + mss."""
+    w = np.zeros(1, dtype=PUSH_FLOW_DTYPE)
+    w["pay_off"], w["unsent"], w["mss"], w["ring_off"], w["cap"], w["q0"] = pay_off, unsent, mss, ring_off, cap, q0
+    w["push"], w["stride"], w["wnd"], w["slot_nxt"] = push, stride or 54 + mss, wnd, slot_nxt
+    w["hdr"][0] = np.frombuffer(bytes(hdr), dtype=np.uint8)
+    return w
+
+
+def push_plan(push: np.ndarray, snd: np.ndarray):
+    """lvlip_push_plan: validates the write sides against the send sides and
+    fills slot0 in place.  Returns (nslots, ring_bytes, nfd); ValueError for a
+    refused plan."""
+    _planned(push, PUSH_FLOW_DTYPE, "push: a writeable contiguous PUSH_FLOW_DTYPE array")
+    _planned(snd, SND_FLOW_DTYPE, "snd: a contiguous SND_FLOW_DTYPE array", writeable=False)
+    if snd.size != push.size:
+        raise ValueError("one send side per write side")
+    ring_bytes, nfd = ctypes.c_uint64(0), ctypes.c_uint32(0)
+    n = _plan_ok(int(_lib.lvlip_push_plan(_aptr(push), _aptr(snd), push.size, ctypes.byref(ring_bytes),
+                                          ctypes.byref(nfd))),
+                 "refused write sides (template, cap, slot_nxt, mss, stride, unsent, wnd, reserved bytes, "
+                 "overlapping regions, a queue outside its region, too many)")
+    return n, int(ring_bytes.value), int(nfd.value)
+
+
+def push_cpu(flows: np.ndarray, lro_res, snd: np.ndarray, push: np.ndarray, payload, base: np.ndarray,
+             fdescs: np.ndarray, sacked=None):
+    """lvlip_push_cpu: compacts every queue to its q0 and appends up to `push`
+    new segments per flow, IN PLACE in snd, push, base (the ring), fdescs and
+    sacked (uint8 per fd index, or None).  lro_res (LRO_RESULT_DTYPE per flow)
+    may be None.  Returns (fd_out, res): FRAME_DESC_DTYPE per slot ({0, 0, 0} =
+    no frame) and PUSH_RESULT_DTYPE per flow."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    _planned(snd, SND_FLOW_DTYPE, "snd: a writeable contiguous SND_FLOW_DTYPE array")
+    _planned(push, PUSH_FLOW_DTYPE, "push: a writeable contiguous PUSH_FLOW_DTYPE array")
+    _planned(fdescs, FRAME_DESC_DTYPE, "fdescs: a writeable contiguous FRAME_DESC_DTYPE array")
+    if snd.size != flows.size or push.size != flows.size:
+        raise ValueError("one send side and one write side per flow")
+    if not _is_u8(base, writeable=True):
+        raise TypeError("base: a writeable contiguous uint8 array (frames are built in place)")
+    if sacked is not None and not _is_u8(sacked, writeable=True):
+        raise TypeError("sacked: a writeable contiguous uint8 array")
+    pay = _u8_inplace(payload)
+    if lro_res is not None:
+        lro_res = np.ascontiguousarray(lro_res, dtype=LRO_RESULT_DTYPE)
+        if lro_res.size != flows.size:
+            raise ValueError("one result per flow")
+    if push.size:
+        if int((push["q0"].astype(np.uint64) + push["cap"]).max()) > min(fdescs.size, sacked.size if sacked is not None
+                                                                         else fdescs.size):
+            raise ValueError("a region lies past fd or sacked")
+        if int((push["ring_off"] + (push["cap"].astype(np.uint64) - 1) * push["stride"] + 54 + push["mss"]).max()) \
+                > base.size:
+            raise ValueError("a slot lies past the ring")
+        if int((push["pay_off"] + push["unsent"]).max()) > pay.size:
+            raise ValueError("unsent bytes lie past the payload")
+    nslots = int(push["push"].astype(np.uint64).sum()) if push.size else 0
+    fd_out = np.zeros(nslots, dtype=FRAME_DESC_DTYPE)
+    res = np.zeros(flows.size, dtype=PUSH_RESULT_DTYPE)
+    _check(_lib.lvlip_push_cpu(_aptr(flows), _aptr(lro_res), _aptr(snd), _aptr(push), flows.size, nslots,
+                               _aptr(pay, True), _aptr(base, True), _aptr(fdescs, True), _aptr(sacked),
+                               _aptr(fd_out, True), _aptr(res)), "lvlip_push_cpu")
+    return fd_out, res
+
+
+def push_dev(flows_t, lro_res_t, snd_t, push_t, nslots: int, payload_t, base_t, fd_t, sacked_t=None, fd_out_t=None,
+             res_t=None, stream=None):
+    """lvlip_push_dev on CUDA uint8 tensors: flows_t 48, snd_t 32 and push_t 112
+    bytes per flow (snd_t and push_t are updated in place), base_t the ring,
+    fd_t its descriptors, sacked_t (may be None) the scoreboard; nslots is what
+    push_plan returned.  lro_res_t (48 bytes per flow) may be None.  Returns
+    (fd_out_t, res_t): 16 bytes per slot and 16 per flow (new tensors unless
+    given).  Three launches on `stream` (default: current), asynchronous."""
+    nflows = _nbytes(flows_t) // LRO_FLOW_DTYPE.itemsize
+    _need(snd_t, "snd_t", SND_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(push_t, "push_t", PUSH_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(lro_res_t, "lro_res_t", LRO_RESULT_DTYPE.itemsize, nflows, "flow", optional=True)
+    fd_out_t = _result(fd_out_t, "fd_out_t", 16, nslots, "slot", base_t.device)
+    res_t = _result(res_t, "res_t", PUSH_RESULT_DTYPE.itemsize, nflows, "flow", base_t.device)
+    s = _stream(stream, base_t.device)
+    _check(_lib.lvlip_push_dev(flows_t.data_ptr(), _tptr(lro_res_t), snd_t.data_ptr(), push_t.data_ptr(), nflows,
+                               nslots, payload_t.data_ptr(), base_t.data_ptr(), fd_t.data_ptr(), _tptr(sacked_t),
+                               fd_out_t.data_ptr(), res_t.data_ptr(), s.cuda_stream), "lvlip_push_dev")
+    return fd_out_t[:16 * nslots], res_t[:PUSH_RESULT_DTYPE.itemsize * nflows]
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
