@@ -1110,6 +1110,194 @@ int lvlip_push_dev(const lvlip_lro_flow *f, const lvlip_lro_result *lro, lvlip_s
                    uint32_t nflows, uint32_t nslots, const void *payload, void *base, lvlip_frame_desc *fd,
                    uint8_t *sacked, lvlip_frame_desc *fd_out, lvlip_push_result *res, void *stream);
 
+/* ---- f2 on the device: the timer and the peer's window ----------------------- */
+
+/* The two decisions of the sender's loop that the calls above leave to the
+ * host: WHEN a flow re-sends (lvlip_rto_*) and HOW FAR it may run ahead of the
+ * peer (lvlip_wnd_*).  With them the loop is ... -> reverse lvlip_lro_* ->
+ * lvlip_snd_* -> lvlip_sack_* -> lvlip_wnd_* -> lvlip_snd_next_* ->
+ * lvlip_push_* -> lvlip_rto_* -> lvlip_rtx_sack_* -> ..., and the application
+ * supplies bytes and one clock value per round.
+ *
+ * lvlip_rto_flow k is the timer and window state of flow k of the reverse
+ * plan, as lvlip_snd_flow k is its send side.  The struct has no padding: every
+ * byte is a field.
+ *
+ * lvlip_rto_* restates, per flow and per round:
+ *   tcp_rtt                      src/tcp.c:424-452 (RFC 6298 2.2, 2.3; the 200 ms
+ *                                floor of :449), with Karn's rule of :426
+ *   tcp_retransmission_timeout   src/tcp_output.c:359-401: the empty queue
+ *                                (:371-375), the 60 s cut-off (:384-391, tcp_done
+ *                                and -ETIMEDOUT), doubling and backoff (:394-396)
+ *   tcp_rearm_rto_timer          on the first skb of an empty queue
+ *                                (src/tcp_output.c:138-140, :417)
+ *   tcp_stop_rto_timer           when the queue empties (src/tcp_input.c:86-89)
+ *   the timer's test             t->expires < tick, src/timer.c:71: strict, and
+ *                                unsigned (expires is a uint32_t there)
+ * The caller starts a flow with rto = 1000 (src/tcp_input.c:196), everything
+ * else 0 but wnd_cap and wscale.
+ *
+ * One call, for flow k, in this fixed order, with nseg = s[k].nseg (the queue
+ * as it now stands), pushed = min(push[k].pushed, nseg) (push may be NULL: 0)
+ * and before = nseg - pushed, the queue before the push:
+ *   1 ACKs   n_new = snd[k].n_new, n_dup = snd[k].n_dup (they survive
+ *            lvlip_snd_next_*; snd may be NULL: both 0).
+ *            n_new > 0: tcp_rtt, then dupacks = 0, then, if before == 0,
+ *            armed = 0 and backoff = 0.  tcp_rtt returns at once when
+ *            backoff > 0 or the timer is not armed; else r = (int32_t)(now -
+ *            (expires - rto)) with the CURRENT rto, which after the first sample
+ *            is no longer the one the timer was armed with: the reference's
+ *            quirk, kept; r < 0 returns.  srtt == 0 (:434, the reference's test
+ *            for "first") : srtt = r, rttvar = r / 2.  Else rttvar = (3 rttvar +
+ *            |srtt - r|) / 4, then srtt = (7 srtt + r) / 8, both truncated
+ *            towards 0.  These equal the reference's double arithmetic for
+ *            every int32_t input: the products by 0.75, 0.25, 0.875 and 0.125
+ *            are exact in a double and its conversion to int truncates the
+ *            same way.  Then k = max(4 rttvar, 200) and rto = srtt + k.
+ *            n_new == 0: dupacks += n_dup.
+ *   2 push   pushed > 0 and before == 0: armed = 1, expires = now + rto.
+ *   3 timer  armed and expires < now: with nseg == 0, armed = 0 and
+ *            backoff = 0 and nothing fires; else the flow FIRES (timeout) and
+ *            either rto > 60000: dead = 1, armed = 0, backoff = 0 (tcp_done
+ *            stops the timer, src/tcp.c:313-334; the head is sent first there
+ *            too), or rto *= 2, backoff++ (a uint8_t, as there),
+ *            expires = now + rto.
+ *   4 fast   only with LVLIP_RTO_FAST and when step 3 did not fire: dupacks was
+ *            below 3 at entry, is at least 3 now, and nseg > 0: the flow FIRES
+ *            (fast).  No timer state changes.  The reference has no fast
+ *            retransmit; this is RFC 5681 section 3.2.
+ * A flow that is dead at entry never fires and nothing of it changes.
+ *
+ * Outputs.  res[k] = {fired, sample, rto, backoff}: fired 0, LVLIP_RTO_TIMEOUT
+ * or LVLIP_RTO_FASTRTX; sample the r that tcp_rtt took, 0xFFFFFFFF when it took
+ * none; rto and backoff as the call leaves them.  gate[k] is a whole
+ * lvlip_snd_result, all zero but popped: 0 for a flow that fired, s[k].nseg for
+ * one that did not.  Passed as `snd` to the unchanged lvlip_rtx_* /
+ * lvlip_rtx_sack_* it makes every slot of a silent flow dead by their own rule
+ * (popped_k + j < nseg), so rtx needs no host step per round.  With a non-NULL
+ * sacked a flow that TIMED OUT has sacked[seg0 .. seg0 + nseg) zeroed (RFC 2018
+ * section 8, the peer may renege; see lvlip_sack_* above); a fast retransmit
+ * keeps the marks; no other byte of the scoreboard is stored.
+ *
+ * Departures from the reference: one `now` per call, with a round's ACKs
+ * ordered before its timer (there each runs when it happens); the dupack count
+ * and the fast retransmit; `dead` stands for tcp_done, which stays on the host.
+ *
+ * lvlip_wnd_* reads the window field of the ACKs.  The reference never does:
+ * src/tcp_input.c:352-354 is a TODO and snd_wnd is written once
+ * (src/tcp_output.c:429).  Reading it is a departure, as reading SACK blocks is.
+ *
+ * Which records count.  Record i counts for flow k = rec[i].flow under the rule
+ * of lvlip_snd_* ("Which records carry an ACK"), when besides d = (ack_seq -
+ * s[k].snd_una) mod 2^32 is at most span = (s[k].snd_nxt - s[k].snd_una) mod
+ * 2^32 (new or duplicate, against the values at call entry), and when its
+ * frame ack_fd[i] passes the test lvlip_sack_* applies before it reads
+ * options: fd.len at least 34, version 4, ihl at least 5, fd.len at least 14 +
+ * ihl*4 + 20, hl at least 5 and fd.len at least 14 + ihl*4 + hl*4.  Only bytes
+ * inside the frame are read: a crafted record changes values, never an address.
+ *
+ * The winner of flow k is the counting record with the largest (d, i), i the
+ * record index: RFC 793's SND.WL1 / SND.WL2 rule (take the window of the
+ * segment that acknowledges most, the later one among equals) reduced to what
+ * a batch can order.  It does not depend on the order the records run in.
+ *
+ * res[k] = {n_counting, winner (0xFFFFFFFF if none), raw, snd_wnd}: raw =
+ * ntohs of the two bytes at 14 + ihl*4 + 14 of the winner's frame (0 without a
+ * winner), and t[k].snd_wnd = min(raw << t[k].wscale, 2^30); a flow without a
+ * winner keeps its snd_wnd; res[k].snd_wnd is t[k].snd_wnd as the call leaves
+ * it.  With LVLIP_WND_APPLY and a non-NULL w, w[k].wnd = min(t[k].snd_wnd,
+ * t[k].wnd_cap) for EVERY flow; nothing else of w and t is written.  wnd_cap is
+ * where a congestion window plugs in.  n == 0 is not a no-op: no flow has a
+ * winner, res is written and the window applied.  Out of scope: the
+ * zero-window persist timer (RFC 1122 4.2.2.17); a flow whose peer closes the
+ * window waits for the next ACK that opens it. */
+#define LVLIP_RTO_FAST    0x1u        /* flags of lvlip_rto_*: step 4 */
+#define LVLIP_RTO_TIMEOUT 1u          /* lvlip_rto_result.fired */
+#define LVLIP_RTO_FASTRTX 2u
+#define LVLIP_RTO_DEAD_MS 60000u      /* src/tcp_output.c:384 */
+#define LVLIP_WND_APPLY   0x1u        /* flags of lvlip_wnd_*: write w[k].wnd */
+#define LVLIP_WSCALE_MAX  14u         /* RFC 7323 2.3 */
+
+typedef struct lvlip_rto_flow {       /* one per planned flow, index k = flow k in plan order; sizeof == 32 */
+    int32_t  srtt, rttvar;            /* tsk->srtt, tsk->rttvar, ms */
+    uint32_t rto;                     /* ms; the caller starts it at 1000 */
+    uint32_t expires;                 /* timer->expires; meaningful while armed */
+    uint32_t dupacks;                 /* duplicate ACKs since the last new one, carried across batches */
+    uint32_t snd_wnd;                 /* the peer's window in bytes, as lvlip_wnd_* last left it; 0 .. 2^30 */
+    uint32_t wnd_cap;                 /* the caller's ceiling on w.wnd, 0 .. 2^30 */
+    uint8_t  armed;                   /* tsk->retransmit != NULL; 0 or 1 */
+    uint8_t  backoff;                 /* tsk->backoff */
+    uint8_t  dead;                    /* sticky, 0 or 1: a timeout found rto > 60000 */
+    uint8_t  wscale;                  /* the peer's window scale, 0 .. 14 */
+} lvlip_rto_flow;
+
+typedef struct lvlip_rto_result {     /* one per planned flow; sizeof == 16 */
+    uint32_t fired, sample, rto, backoff;
+} lvlip_rto_result;
+
+typedef struct lvlip_wnd_result {     /* one per planned flow; sizeof == 16 */
+    uint32_t n_counting, winner, raw, snd_wnd;
+} lvlip_wnd_result;
+
+/* Host only: 0 when every t[k] is a state these calls take, LVLIP_EINVAL for a
+ * wscale above 14, snd_wnd or wnd_cap above 2^30, armed or dead other than 0
+ * and 1, a NULL t with nflows > 0 or nflows above LVLIP_LRO_MAX_FLOWS.  The
+ * _dev forms cannot look: the state is in HBM; the caller checks it here before
+ * it uploads it, as the plans check theirs.  Nothing is written. */
+int lvlip_rto_check(const lvlip_rto_flow *t, uint32_t nflows);
+
+/* On the calling thread.  f, s: the planned reverse flows and their send sides
+ * as lvlip_snd_* takes them (read only); t, w (may be NULL) and res are
+ * written as above; rec[i] is the record of frame ack_fd[i] inside ack_base.
+ * Returns 0, or LVLIP_EINVAL with nothing written: NULL f, s, t or res with
+ * nflows > 0, NULL rec, ack_base or ack_fd with n > 0, n above LVLIP_MAX_BATCH,
+ * nflows above LVLIP_LRO_MAX_FLOWS, flag bits other than LVLIP_WND_APPLY, or a
+ * t lvlip_rto_check refuses.  nflows == 0 is a no-op.  Reentrant. */
+int lvlip_wnd_cpu(const lvlip_lro_flow *f, const lvlip_snd_flow *s, lvlip_rto_flow *t, lvlip_push_flow *w,
+                  uint32_t nflows, const lvlip_lro_rec *rec, const void *ack_base, const lvlip_frame_desc *ack_fd,
+                  uint32_t n, uint32_t flags, lvlip_wnd_result *res);
+
+/* The same bytes of res, t and w on the caller's stream (asynchronous; no
+ * allocation, copy, synchronisation or LDS, no workspace beyond res): res is
+ * zeroed, a lane per record raises its flow's 64-bit key (d + 1) << 32 | i
+ * with one atomic max and counts with one atomic add (records of one flow are
+ * first reduced within their wave, as in lvlip_snd_dev; max and add only, so
+ * the bytes do not depend on the run), and a lane per flow reads the winner's
+ * window and writes res, t and w.  All pointers are device pointers: f, s, t
+ * and w 8-B aligned, rec, ack_fd and res 16-B aligned, ack_base any alignment.
+ * The NULL, limit and flag refusals of lvlip_wnd_cpu and a misaligned pointer
+ * are LVLIP_EINVAL before any HIP call (t is not looked at: lvlip_rto_check);
+ * LVLIP_ENODEV without a device; a failed launch is LVLIP_EHIP
+ * (lvlip_last_hip_error).  Measured: DESIGN.md section 9j. */
+int lvlip_wnd_dev(const lvlip_lro_flow *f, const lvlip_snd_flow *s, lvlip_rto_flow *t, lvlip_push_flow *w,
+                  uint32_t nflows, const lvlip_lro_rec *rec, const void *ack_base, const lvlip_frame_desc *ack_fd,
+                  uint32_t n, uint32_t flags, lvlip_wnd_result *res, void *stream);
+
+/* On the calling thread, once per round, after lvlip_snd_next_* and
+ * lvlip_push_*.  s, snd (may be NULL) and push (may be NULL) are read; t,
+ * gate, res and, if given, sacked (one byte per fd index, any alignment) are
+ * written as above.  Returns 0, or LVLIP_EINVAL with nothing written: NULL s,
+ * t, gate or res with nflows > 0, nflows above LVLIP_LRO_MAX_FLOWS, flag bits
+ * other than LVLIP_RTO_FAST, or a t lvlip_rto_check refuses.  nflows == 0 is a
+ * no-op.  Reentrant. */
+int lvlip_rto_cpu(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lvlip_push_result *push,
+                  lvlip_rto_flow *t, uint32_t nflows, uint32_t now, uint32_t flags, uint8_t *sacked,
+                  lvlip_snd_result *gate, lvlip_rto_result *res);
+
+/* The same bytes in ONE launch on the caller's stream (asynchronous; no
+ * allocation, copy, atomics, LDS, workspace or synchronisation): a wave per
+ * flow, four per workgroup; lane 0 does the arithmetic and the 16- and 32-byte
+ * stores, and the wave clears a timed-out flow's scoreboard range 64 bytes a
+ * step.  All pointers are device pointers: s and t 8-B aligned, snd, push, gate
+ * and res 16-B aligned, sacked any alignment.  The NULL, limit and flag
+ * refusals of lvlip_rto_cpu and a misaligned pointer are LVLIP_EINVAL before
+ * any HIP call (t is not looked at: lvlip_rto_check); LVLIP_ENODEV without a
+ * device; a failed launch is LVLIP_EHIP (lvlip_last_hip_error).  Measured:
+ * DESIGN.md section 9j. */
+int lvlip_rto_dev(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lvlip_push_result *push,
+                  lvlip_rto_flow *t, uint32_t nflows, uint32_t now, uint32_t flags, uint8_t *sacked,
+                  lvlip_snd_result *gate, lvlip_rto_result *res, void *stream);
+
 /* RFC 1071 pseudo-header seed with the carries folded back (for RX verify of
  * checksums produced by RFC-correct peers). */
 uint32_t lvlip_pseudo_sum_rfc(uint32_t saddr, uint32_t daddr, uint8_t proto,

@@ -258,6 +258,12 @@ SIGNATURES = {
     "lvlip_push_plan": (_U32, [_P, _P, _U32, _PU64, _PU32]),
     "lvlip_push_cpu": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P]),
     "lvlip_push_dev": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    # f2 on the device: the timer and the peer's window (rto_cpu.c, rto_kernels.hip)
+    "lvlip_rto_check": (_INT, [_P, _U32]),
+    "lvlip_wnd_cpu": (_INT, [_P, _P, _P, _P, _U32, _P, _P, _P, _U32, _U32, _P]),
+    "lvlip_wnd_dev": (_INT, [_P, _P, _P, _P, _U32, _P, _P, _P, _U32, _U32, _P, _P]),
+    "lvlip_rto_cpu": (_INT, [_P, _P, _P, _P, _U32, _U32, _U32, _P, _P, _P]),
+    "lvlip_rto_dev": (_INT, [_P, _P, _P, _P, _U32, _U32, _U32, _P, _P, _P, _P]),
     "lvlip_auto_kernel": (_INT, [_I32, _U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (_U32, [_U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (_STR, []),
@@ -1298,6 +1304,132 @@ def push_dev(flows_t, lro_res_t, snd_t, push_t, nslots: int, payload_t, base_t, 
                                nslots, payload_t.data_ptr(), base_t.data_ptr(), fd_t.data_ptr(), _tptr(sacked_t),
                                fd_out_t.data_ptr(), res_t.data_ptr(), s.cuda_stream), "lvlip_push_dev")
     return fd_out_t[:16 * nslots], res_t[:PUSH_RESULT_DTYPE.itemsize * nflows]
+
+
+# ------------------------ f2 on the device: the timer and the peer's window --
+
+# struct lvlip_rto_flow (32 B) / lvlip_rto_result / lvlip_wnd_result (16 B each), include/lvlip_skb.h
+RTO_FLOW_DTYPE = np.dtype([("srtt", "<i4"), ("rttvar", "<i4"), ("rto", "<u4"), ("expires", "<u4"),
+                           ("dupacks", "<u4"), ("snd_wnd", "<u4"), ("wnd_cap", "<u4"), ("armed", "u1"),
+                           ("backoff", "u1"), ("dead", "u1"), ("wscale", "u1")])
+RTO_RESULT_DTYPE = np.dtype([("fired", "<u4"), ("sample", "<u4"), ("rto", "<u4"), ("backoff", "<u4")])
+WND_RESULT_DTYPE = np.dtype([("n_counting", "<u4"), ("winner", "<u4"), ("raw", "<u4"), ("snd_wnd", "<u4")])
+RTO_FAST, RTO_TIMEOUT, RTO_FASTRTX, RTO_NO_SAMPLE = 1, 1, 2, 0xFFFFFFFF
+WND_APPLY, WND_NO_WINNER = 1, 0xFFFFFFFF
+assert RTO_FLOW_DTYPE.itemsize == 32 and RTO_RESULT_DTYPE.itemsize == 16 and WND_RESULT_DTYPE.itemsize == 16
+
+
+def rto_flows(nflows: int, rto: int = 1000, wnd_cap: int = PUSH_NO_LIMIT, snd_wnd: int = PUSH_NO_LIMIT,
+              wscale: int = 0) -> np.ndarray:
+    """nflows fresh lvlip_rto_flow states: rto 1000 ms (src/tcp_input.c:196),
+    no sample, no timer, the window open until an ACK says otherwise."""
+    t = np.zeros(nflows, dtype=RTO_FLOW_DTYPE)
+    t["rto"], t["wnd_cap"], t["snd_wnd"], t["wscale"] = rto, wnd_cap, snd_wnd, wscale
+    return t
+
+
+def rto_check(rto: np.ndarray) -> None:
+    """lvlip_rto_check: ValueError for a state the calls refuse."""
+    _planned(rto, RTO_FLOW_DTYPE, "rto: a contiguous RTO_FLOW_DTYPE array", writeable=False)
+    if _lib.lvlip_rto_check(_aptr(rto), rto.size) != OK:
+        raise ValueError("refused timer state (wscale, snd_wnd, wnd_cap, armed, dead, too many)")
+
+
+def wnd_cpu(flows: np.ndarray, snd: np.ndarray, rto: np.ndarray, push, rec: np.ndarray, ack_base,
+            ack_fdescs: np.ndarray, flags: int = 0) -> np.ndarray:
+    """lvlip_wnd_cpu: the peer's window from the ACK frames ack_fdescs inside
+    ack_base (rec their records), IN PLACE in rto["snd_wnd"] and, with
+    WND_APPLY, in push["wnd"] (push may be None).  Returns WND_RESULT_DTYPE per
+    flow."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    snd = np.ascontiguousarray(snd, dtype=SND_FLOW_DTYPE)
+    rec = np.ascontiguousarray(rec, dtype=LRO_REC_DTYPE)
+    _planned(rto, RTO_FLOW_DTYPE, "rto: a writeable contiguous RTO_FLOW_DTYPE array")
+    if push is not None:
+        _planned(push, PUSH_FLOW_DTYPE, "push: a writeable contiguous PUSH_FLOW_DTYPE array")
+    if snd.size != flows.size or rto.size != flows.size or (push is not None and push.size != flows.size):
+        raise ValueError("one send side, one timer state and one write side per flow")
+    abuf = _u8_inplace(ack_base)
+    afd = np.ascontiguousarray(ack_fdescs, dtype=FRAME_DESC_DTYPE)
+    if afd.size != rec.size:
+        raise ValueError("one record per ACK frame")
+    if (afd["offset"] + afd["len"].astype(np.uint64) > abuf.size).any():
+        raise ValueError("an ACK frame lies past ack_base")
+    res = np.zeros(flows.size, dtype=WND_RESULT_DTYPE)
+    _check(_lib.lvlip_wnd_cpu(_aptr(flows), _aptr(snd), _aptr(rto), _aptr(push), flows.size, _aptr(rec),
+                              _aptr(abuf, True) if rec.size else None, _aptr(afd), rec.size, flags, _aptr(res)),
+           "lvlip_wnd_cpu")
+    return res
+
+
+def wnd_dev(flows_t, snd_t, rto_t, push_t, rec_t, ack_base_t, ack_fd_t, flags: int = 0, res_t=None, stream=None):
+    """lvlip_wnd_dev on CUDA uint8 tensors: flows_t 48, snd_t 32, rto_t 32 and
+    push_t (may be None) 112 bytes per flow; rto_t and push_t are updated in
+    place.  rec_t 16 bytes per ACK frame, ack_fd_t their descriptors inside
+    ack_base_t.  Returns res_t, 16 bytes per flow (a new tensor unless given).
+    Asynchronous on `stream` (default: current)."""
+    nflows = _nbytes(flows_t) // LRO_FLOW_DTYPE.itemsize
+    n = _records(rec_t, 16)
+    _need(snd_t, "snd_t", SND_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(rto_t, "rto_t", RTO_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(push_t, "push_t", PUSH_FLOW_DTYPE.itemsize, nflows, "flow", optional=True)
+    if n:
+        _need(ack_fd_t, "ack_fd_t", 16, n, "record")
+    res_t = _result(res_t, "res_t", WND_RESULT_DTYPE.itemsize, nflows, "flow", flows_t.device, zeroed=True)
+    s = _stream(stream, flows_t.device)
+    _check(_lib.lvlip_wnd_dev(flows_t.data_ptr(), snd_t.data_ptr(), rto_t.data_ptr(), _tptr(push_t), nflows,
+                              _tptr(rec_t, n), ack_base_t.data_ptr() if n else None,
+                              ack_fd_t.data_ptr() if n else None, n, flags, res_t.data_ptr(), s.cuda_stream),
+           "lvlip_wnd_dev")
+    return res_t[:WND_RESULT_DTYPE.itemsize * nflows]
+
+
+def rto_cpu(snd: np.ndarray, snd_res, push_res, rto: np.ndarray, now: int, flags: int = 0, sacked=None):
+    """lvlip_rto_cpu: one round of the retransmission timer, IN PLACE in rto
+    and, for flows that timed out, in `sacked` (uint8 per fd index, or None).
+    snd as snd_next_* / push_* left it; snd_res (SND_RESULT_DTYPE) and push_res
+    (PUSH_RESULT_DTYPE) may be None.  Returns (gate, res): the SND_RESULT_DTYPE
+    array to hand to rtx_* / rtx_sack_* as snd_res, and RTO_RESULT_DTYPE per
+    flow."""
+    snd = np.ascontiguousarray(snd, dtype=SND_FLOW_DTYPE)
+    _planned(rto, RTO_FLOW_DTYPE, "rto: a writeable contiguous RTO_FLOW_DTYPE array")
+    if snd_res is not None:
+        snd_res = np.ascontiguousarray(snd_res, dtype=SND_RESULT_DTYPE)
+    if push_res is not None:
+        push_res = np.ascontiguousarray(push_res, dtype=PUSH_RESULT_DTYPE)
+    if rto.size != snd.size or any(r is not None and r.size != snd.size for r in (snd_res, push_res)):
+        raise ValueError("one timer state and one result per flow")
+    if sacked is not None:
+        if not _is_u8(sacked, writeable=True):
+            raise TypeError("sacked: a writeable contiguous uint8 array")
+        ends = snd["seg0"].astype(np.uint64) + snd["nseg"]
+        if ((snd["nseg"] > 0) & (ends > sacked.size)).any():
+            raise ValueError("a queue lies past sacked")
+    gate = np.zeros(snd.size, dtype=SND_RESULT_DTYPE)
+    res = np.zeros(snd.size, dtype=RTO_RESULT_DTYPE)
+    _check(_lib.lvlip_rto_cpu(_aptr(snd), _aptr(snd_res), _aptr(push_res), _aptr(rto), snd.size, now & 0xFFFFFFFF,
+                              flags, _aptr(sacked), _aptr(gate), _aptr(res)), "lvlip_rto_cpu")
+    return gate, res
+
+
+def rto_dev(snd_t, snd_res_t, push_res_t, rto_t, now: int, flags: int = 0, sacked_t=None, gate_t=None, res_t=None,
+            stream=None):
+    """lvlip_rto_dev on CUDA uint8 tensors: snd_t 32 and rto_t 32 bytes per
+    flow (rto_t updated in place), snd_res_t (32 per flow) and push_res_t (16
+    per flow) may be None, sacked_t (may be None) the scoreboard.  Returns
+    (gate_t, res_t): 32 and 16 bytes per flow (new tensors unless given).  One
+    launch on `stream` (default: current), asynchronous."""
+    nflows = _nbytes(snd_t) // SND_FLOW_DTYPE.itemsize
+    _need(rto_t, "rto_t", RTO_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(snd_res_t, "snd_res_t", SND_RESULT_DTYPE.itemsize, nflows, "flow", optional=True)
+    _need(push_res_t, "push_res_t", PUSH_RESULT_DTYPE.itemsize, nflows, "flow", optional=True)
+    gate_t = _result(gate_t, "gate_t", SND_RESULT_DTYPE.itemsize, nflows, "flow", snd_t.device)
+    res_t = _result(res_t, "res_t", RTO_RESULT_DTYPE.itemsize, nflows, "flow", snd_t.device)
+    s = _stream(stream, snd_t.device)
+    _check(_lib.lvlip_rto_dev(snd_t.data_ptr(), _tptr(snd_res_t), _tptr(push_res_t), rto_t.data_ptr(), nflows,
+                              now & 0xFFFFFFFF, flags, _tptr(sacked_t), gate_t.data_ptr(), res_t.data_ptr(),
+                              s.cuda_stream), "lvlip_rto_dev")
+    return gate_t[:SND_RESULT_DTYPE.itemsize * nflows], res_t[:RTO_RESULT_DTYPE.itemsize * nflows]
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
