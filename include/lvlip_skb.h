@@ -1298,6 +1298,140 @@ int lvlip_rto_dev(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lv
                   lvlip_rto_flow *t, uint32_t nflows, uint32_t now, uint32_t flags, uint8_t *sacked,
                   lvlip_snd_result *gate, lvlip_rto_result *res, void *stream);
 
+/* ---- f2 on the device: the congestion window --------------------------------
+ *
+ * lvlip_push_* sends up to w.wnd bytes past snd_una and lvlip_wnd_* sets that
+ * to min(snd_wnd, t.wnd_cap).  lvlip_cc_* writes t[k].wnd_cap once per round:
+ * the congestion window of RFC 5681 (slow start, congestion avoidance, the
+ * cut on a timeout) with RFC 3465's byte counting, the recovery point of RFC
+ * 6582 and the pipe of RFC 6675, from what the other calls already leave on the
+ * device: lvlip_snd_result.acked / n_new, lvlip_rto_result.fired / backoff,
+ * the scoreboard of lvlip_sack_* and the queue's fd[].  The reference has a
+ * cwnd field (include/tcp.h:211) that it never reads or writes: like reading
+ * SACK blocks and the window field, this is a departure that follows the RFCs.
+ *
+ * lvlip_cc_flow k is the congestion state of flow k of the reverse plan, as
+ * lvlip_rto_flow k is its timer.  The struct has no padding.  The caller starts
+ * a flow with cwnd at the initial window (RFC 5681 3.1: min(4 mss, max(2 mss,
+ * 4380))), ssthresh = 2^30, its mss and ceiling, everything else 0.
+ *
+ * Where it sits in the loop.  After lvlip_sack_* and before lvlip_wnd_* and
+ * lvlip_snd_next_*: snd[k].acked and popped are still unconsumed there; s[k] is
+ * as the previous round's lvlip_rto_* saw it, because nothing between them
+ * writes s; prev is the previous round's lvlip_rto_result array.  lvlip_wnd_*
+ * with LVLIP_WND_APPLY then carries t[k].wnd_cap into w[k].wnd, unchanged.
+ *
+ * One call, for flow k, in this fixed order, with
+ *   flight = (s.snd_nxt - s.snd_una) mod 2^32
+ *   a = snd[k].acked, n_new = snd[k].n_new      (snd may be NULL: both 0)
+ *   fired = prev[k].fired, bo = prev[k].backoff (prev may be NULL: both 0)
+ *   half = max(flight / 2, 2 mss)
+ * A flow with t[k].dead set: c[k] and t[k] do not change, res[k] = {c.cwnd, 0,
+ * 0, 0}.  Otherwise:
+ *   1 loss   from the previous round's timer.
+ *            fired == LVLIP_RTO_TIMEOUT: ssthresh = half only when bo == 1 (RFC
+ *            5681 3.1: a segment that times out again does not halve twice);
+ *            always cwnd = mss, acc = 0, in_rec = 0, recover = s.snd_nxt; event
+ *            TIMEOUT.
+ *            fired == LVLIP_RTO_FASTRTX and in_rec == 0: ssthresh = half, cwnd =
+ *            ssthresh, acc = 0, in_rec = 1, recover = s.snd_nxt; event ENTER (RFC
+ *            6675 5, step 4.2).  FASTRTX while in_rec == 1 changes nothing.
+ *   2 ACKs   only when n_new > 0 and a > 0.
+ *            in_rec == 1: a full ACK, a >= (recover - s.snd_una) mod 2^32, sets
+ *            in_rec = 0, cwnd = ssthresh, acc = 0; event EXIT.  A partial ACK
+ *            changes nothing: the pipe of step 3 governs what goes out.
+ *            in_rec == 0 and cwnd < ssthresh: cwnd += min(a, n_new * mss),
+ *            formed in 64 bits (RFC 5681 eq. 2 summed over the batch's ACKs);
+ *            event SLOWSTART.
+ *            in_rec == 0 otherwise: acc += a (64 bits); if acc >= cwnd then
+ *            acc -= cwnd, cwnd += mss, event AVOID, once per call (a batch is
+ *            a round and RFC 5681 allows one mss per RTT); then acc = min(acc,
+ *            cwnd).
+ *            Finally cwnd = min(cwnd, cwnd_max), whichever of the three ran and
+ *            whether it changed anything.  No loops: the step takes the same
+ *            time for every input.
+ *   3 pipe   p = min(snd[k].popped, s.nseg).  Over the queue entries q in
+ *            [seg0 + p, seg0 + nseg), the index formed in 64 bits: n_sacked
+ *            counts the entries with sacked[q] != 0 (the test of
+ *            lvlip_rtx_sack_*), sacked_bytes sums fd[q].len - 54 over those of
+ *            them with fd[q].len >= 54, in 64 bits, clamped to 2^30.  A NULL
+ *            sacked gives both 0.
+ *   4 output t[k].wnd_cap = min(cwnd + sacked_bytes, 2^30): the bytes the peer
+ *            reports holding are not in the network, so bounding snd_nxt -
+ *            snd_una by this bounds RFC 6675's pipe by cwnd.  res[k] = {cwnd,
+ *            sacked_bytes, n_sacked, event}.  Nothing else of t is written.
+ *
+ * Limits.  Step 3 reads fd and sacked only, never the ring: an entry's payload
+ * is taken as fd.len - 54, the header of every frame lvlip_tso_* and
+ * lvlip_push_* build; a queue of frames with IP or TCP options is overcounted
+ * by their length.  s is not validated again (the caller planned it), and
+ * neither is what the arithmetic leaves: a caller who hands in in_rec = 1 with
+ * ssthresh below mss gets that back as cwnd on the full ACK, and step 1 does
+ * not apply cwnd_max; lvlip_cc_check says so before the next call.
+ *
+ * Departures.  The reference has no congestion control.  One step per batch,
+ * not per ACK.  No retransmit of the next hole on a partial ACK:
+ * lvlip_rtx_sack_* with rtx > 1 re-sends several holes when the flow fires, and
+ * the timer covers the rest.  No ECN, no pacing, no persist timer. */
+#define LVLIP_CC_MAX_WND 0x40000000u
+/* event bits of lvlip_cc_result.event */
+#define LVLIP_CC_EV_TIMEOUT   0x01u   /* step 1 cut cwnd to one mss */
+#define LVLIP_CC_EV_ENTER     0x02u   /* entered fast recovery */
+#define LVLIP_CC_EV_EXIT      0x04u   /* full ACK: left fast recovery */
+#define LVLIP_CC_EV_SLOWSTART 0x08u   /* cwnd grew in slow start */
+#define LVLIP_CC_EV_AVOID     0x10u   /* cwnd grew in congestion avoidance */
+
+typedef struct lvlip_cc_flow {        /* one per planned reverse flow; sizeof == 32, no padding */
+    uint32_t cwnd;                    /* bytes, mss .. 2^30 */
+    uint32_t ssthresh;                /* bytes, 0 .. 2^30; the caller starts it at 2^30 */
+    uint32_t recover;                 /* host order: snd_nxt when recovery was entered (RFC 6582) */
+    uint32_t acc;                     /* bytes acknowledged since cwnd last grew in avoidance (RFC 3465 2.1) */
+    uint32_t cwnd_max;                /* the caller's ceiling, mss .. 2^30 */
+    uint16_t mss;                     /* 1 .. 65495 */
+    uint8_t  in_rec;                  /* 0 or 1 */
+    uint8_t  reserved;                /* 0 */
+    uint32_t reserved2[2];            /* 0 */
+} lvlip_cc_flow;
+
+typedef struct lvlip_cc_result {      /* one per planned flow; sizeof == 16 */
+    uint32_t cwnd, sacked_bytes, n_sacked, event;
+} lvlip_cc_result;
+
+/* Host only: 0 when every c[k] is a state these calls take, LVLIP_EINVAL for
+ * mss == 0 or above 65495, cwnd or cwnd_max outside [mss, 2^30], ssthresh above
+ * 2^30, in_rec other than 0 and 1, nonzero reserved bytes, a NULL c with
+ * nflows > 0 or nflows above LVLIP_LRO_MAX_FLOWS.  The _dev form cannot look:
+ * the state is in HBM; the caller checks it here before it uploads it.  Nothing
+ * is written. */
+int lvlip_cc_check(const lvlip_cc_flow *c, uint32_t nflows);
+
+/* On the calling thread.  s, snd (may be NULL), prev (may be NULL), fd and
+ * sacked (one byte per fd index, any alignment; may be NULL, and then fd may
+ * be) are read; c, t[k].wnd_cap and res are written as above.  Returns 0, or
+ * LVLIP_EINVAL with nothing written: NULL s, c, t or res with nflows > 0, NULL
+ * fd with a non-NULL sacked, nflows above LVLIP_LRO_MAX_FLOWS, or a c
+ * lvlip_cc_check refuses.  nflows == 0 is a no-op.  Reentrant. */
+int lvlip_cc_cpu(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lvlip_rto_result *prev,
+                 lvlip_cc_flow *c, lvlip_rto_flow *t, uint32_t nflows, const lvlip_frame_desc *fd,
+                 const uint8_t *sacked, lvlip_cc_result *res);
+
+/* The same bytes of c, t and res on the caller's stream (asynchronous; no
+ * allocation, copy, synchronisation or LDS, no workspace beyond res): res is
+ * zeroed; with a non-NULL sacked a wave per flow and chunk of its queue (a
+ * queue is spread over 8 to 1024 waves by the flow count, as in lvlip_sack_dev)
+ * reads one scoreboard byte per lane and the descriptor of a marked entry
+ * only, and adds its sums to res[k] with one 64-bit and one 32-bit atomic add
+ * (integer adds only, so the bytes do not depend on the run); then a lane per
+ * flow does steps 1, 2 and 4.  All pointers are device pointers: s, c and t
+ * 8-B aligned, snd, prev, fd and res 16-B aligned, sacked any alignment.  The
+ * NULL and limit refusals of lvlip_cc_cpu and a misaligned pointer are
+ * LVLIP_EINVAL before any HIP call (c is not looked at: lvlip_cc_check);
+ * LVLIP_ENODEV without a device; a failed launch is LVLIP_EHIP
+ * (lvlip_last_hip_error).  Measured: DESIGN.md section 9k. */
+int lvlip_cc_dev(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lvlip_rto_result *prev,
+                 lvlip_cc_flow *c, lvlip_rto_flow *t, uint32_t nflows, const lvlip_frame_desc *fd,
+                 const uint8_t *sacked, lvlip_cc_result *res, void *stream);
+
 /* RFC 1071 pseudo-header seed with the carries folded back (for RX verify of
  * checksums produced by RFC-correct peers). */
 uint32_t lvlip_pseudo_sum_rfc(uint32_t saddr, uint32_t daddr, uint8_t proto,

@@ -264,6 +264,10 @@ SIGNATURES = {
     "lvlip_wnd_dev": (_INT, [_P, _P, _P, _P, _U32, _P, _P, _P, _U32, _U32, _P, _P]),
     "lvlip_rto_cpu": (_INT, [_P, _P, _P, _P, _U32, _U32, _U32, _P, _P, _P]),
     "lvlip_rto_dev": (_INT, [_P, _P, _P, _P, _U32, _U32, _U32, _P, _P, _P, _P]),
+    # f2 on the device: the congestion window (cc_cpu.c, cc_kernels.hip)
+    "lvlip_cc_check": (_INT, [_P, _U32]),
+    "lvlip_cc_cpu": (_INT, [_P, _P, _P, _P, _P, _U32, _P, _P, _P]),
+    "lvlip_cc_dev": (_INT, [_P, _P, _P, _P, _P, _U32, _P, _P, _P, _P]),
     "lvlip_auto_kernel": (_INT, [_I32, _U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (_U32, [_U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (_STR, []),
@@ -1430,6 +1434,92 @@ def rto_dev(snd_t, snd_res_t, push_res_t, rto_t, now: int, flags: int = 0, sacke
                               now & 0xFFFFFFFF, flags, _tptr(sacked_t), gate_t.data_ptr(), res_t.data_ptr(),
                               s.cuda_stream), "lvlip_rto_dev")
     return gate_t[:SND_RESULT_DTYPE.itemsize * nflows], res_t[:RTO_RESULT_DTYPE.itemsize * nflows]
+
+
+# ------------------------------------ f2 on the device: the congestion window --
+
+# struct lvlip_cc_flow (32 B) / lvlip_cc_result (16 B), include/lvlip_skb.h
+CC_FLOW_DTYPE = np.dtype([("cwnd", "<u4"), ("ssthresh", "<u4"), ("recover", "<u4"), ("acc", "<u4"),
+                          ("cwnd_max", "<u4"), ("mss", "<u2"), ("in_rec", "u1"), ("reserved", "u1"),
+                          ("reserved2", "<u4", (2,))])
+CC_RESULT_DTYPE = np.dtype([("cwnd", "<u4"), ("sacked_bytes", "<u4"), ("n_sacked", "<u4"), ("event", "<u4")])
+CC_FLOW, CC_RESULT = CC_FLOW_DTYPE, CC_RESULT_DTYPE
+CC_MAX_WND = 0x40000000
+CC_EV_TIMEOUT, CC_EV_ENTER, CC_EV_EXIT, CC_EV_SLOWSTART, CC_EV_AVOID = 0x01, 0x02, 0x04, 0x08, 0x10
+assert CC_FLOW_DTYPE.itemsize == 32 and CC_RESULT_DTYPE.itemsize == 16
+
+
+def cc_init(mss, cwnd_max: int = CC_MAX_WND, nflows: Optional[int] = None) -> np.ndarray:
+    """Fresh lvlip_cc_flow states, one per entry of mss (or nflows of one mss):
+    cwnd at RFC 5681's initial window min(4 mss, max(2 mss, 4380)), held to
+    cwnd_max, ssthresh 2^30."""
+    m = np.atleast_1d(np.asarray(mss, dtype=np.int64))
+    if nflows is not None:
+        m = np.broadcast_to(m, (nflows,))
+    c = np.zeros(m.size, dtype=CC_FLOW_DTYPE)
+    c["mss"], c["cwnd_max"], c["ssthresh"] = m, cwnd_max, CC_MAX_WND
+    c["cwnd"] = np.minimum(np.minimum(4 * m, np.maximum(2 * m, 4380)), c["cwnd_max"])
+    return c
+
+
+def cc_check(cc: np.ndarray) -> None:
+    """lvlip_cc_check: ValueError for a state the calls refuse."""
+    _planned(cc, CC_FLOW_DTYPE, "cc: a contiguous CC_FLOW_DTYPE array", writeable=False)
+    if _lib.lvlip_cc_check(_aptr(cc), cc.size) != OK:
+        raise ValueError("refused congestion state (mss, cwnd, cwnd_max, ssthresh, in_rec, reserved, too many)")
+
+
+def cc_cpu(snd: np.ndarray, snd_res, prev, cc: np.ndarray, rto: np.ndarray, fdescs=None, sacked=None) -> np.ndarray:
+    """lvlip_cc_cpu: one round of the congestion window, IN PLACE in cc and in
+    rto["wnd_cap"].  snd as the previous round's rto_* saw it; snd_res
+    (SND_RESULT_DTYPE, before snd_next_*) and prev (the previous round's
+    RTO_RESULT_DTYPE) may be None; sacked (uint8 per fd index) may be None, and
+    then fdescs may be.  Returns CC_RESULT_DTYPE per flow."""
+    snd = np.ascontiguousarray(snd, dtype=SND_FLOW_DTYPE)
+    _planned(cc, CC_FLOW_DTYPE, "cc: a writeable contiguous CC_FLOW_DTYPE array")
+    _planned(rto, RTO_FLOW_DTYPE, "rto: a writeable contiguous RTO_FLOW_DTYPE array")
+    if snd_res is not None:
+        snd_res = np.ascontiguousarray(snd_res, dtype=SND_RESULT_DTYPE)
+    if prev is not None:
+        prev = np.ascontiguousarray(prev, dtype=RTO_RESULT_DTYPE)
+    if cc.size != snd.size or rto.size != snd.size or any(r is not None and r.size != snd.size
+                                                          for r in (snd_res, prev)):
+        raise ValueError("one congestion state, one timer state and one result per flow")
+    if sacked is not None:
+        if not _is_u8(sacked) or fdescs is None:
+            raise TypeError("sacked: a contiguous uint8 array, with the queue's descriptors")
+        fdescs = np.ascontiguousarray(fdescs, dtype=FRAME_DESC_DTYPE)
+        ends = snd["seg0"].astype(np.uint64) + snd["nseg"]
+        if ((snd["nseg"] > 0) & (ends > min(sacked.size, fdescs.size))).any():
+            raise ValueError("a queue lies past sacked or fdescs")
+    elif fdescs is not None:
+        fdescs = np.ascontiguousarray(fdescs, dtype=FRAME_DESC_DTYPE)
+    res = np.zeros(snd.size, dtype=CC_RESULT_DTYPE)
+    _check(_lib.lvlip_cc_cpu(_aptr(snd), _aptr(snd_res), _aptr(prev), _aptr(cc), _aptr(rto), snd.size,
+                             _aptr(fdescs, sacked is not None), _aptr(sacked, sacked is not None), _aptr(res)),
+           "lvlip_cc_cpu")
+    return res
+
+
+def cc_dev(snd_t, snd_res_t, prev_t, cc_t, rto_t, fd_t=None, sacked_t=None, res_t=None, stream=None):
+    """lvlip_cc_dev on CUDA uint8 tensors: snd_t 32, cc_t 32 and rto_t 32 bytes
+    per flow (cc_t and rto_t's wnd_cap updated in place); snd_res_t (32 per
+    flow) and prev_t (16 per flow) may be None; sacked_t (may be None, and then
+    fd_t may be) the scoreboard of the queue entries fd_t.  Returns res_t, 16
+    bytes per flow (a new tensor unless given).  Asynchronous on `stream`
+    (default: current)."""
+    nflows = _nbytes(snd_t) // SND_FLOW_DTYPE.itemsize
+    _need(cc_t, "cc_t", CC_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(rto_t, "rto_t", RTO_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(snd_res_t, "snd_res_t", SND_RESULT_DTYPE.itemsize, nflows, "flow", optional=True)
+    _need(prev_t, "prev_t", RTO_RESULT_DTYPE.itemsize, nflows, "flow", optional=True)
+    if sacked_t is not None and fd_t is None:
+        raise TypeError("sacked_t needs the queue's descriptors fd_t")
+    res_t = _result(res_t, "res_t", CC_RESULT_DTYPE.itemsize, nflows, "flow", snd_t.device)
+    s = _stream(stream, snd_t.device)
+    _check(_lib.lvlip_cc_dev(snd_t.data_ptr(), _tptr(snd_res_t), _tptr(prev_t), cc_t.data_ptr(), rto_t.data_ptr(),
+                             nflows, _tptr(fd_t), _tptr(sacked_t), res_t.data_ptr(), s.cuda_stream), "lvlip_cc_dev")
+    return res_t[:CC_RESULT_DTYPE.itemsize * nflows]
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
