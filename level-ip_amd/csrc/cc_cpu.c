@@ -7,10 +7,8 @@
  * never touched); the steps are RFC 5681 (slow start, avoidance, the cut on a
  * timeout), RFC 3465 (byte counting), RFC 6582 (recover) and RFC 6675 (pipe).
  */
-#include "lvlip_skb.h"
-
-#define CC_HDR 54u /* the header of every frame lvlip_tso_* / lvlip_push_* build */
-#define CC_MSS_MAX 65495u
+#include "flow_step.h"
+#include "tcp_hdr.h" /* TCP_FRAME_HDR, the header of every frame lvlip_tso_* / lvlip_push_* build; TCP_MSS_MAX */
 
 int lvlip_cc_check(const lvlip_cc_flow *c, uint32_t nflows)
 {
@@ -18,7 +16,7 @@ int lvlip_cc_check(const lvlip_cc_flow *c, uint32_t nflows)
     if (!c || nflows > LVLIP_LRO_MAX_FLOWS) return LVLIP_EINVAL;
     for (uint32_t k = 0; k < nflows; k++) {
         const uint32_t mss = c[k].mss;
-        if (mss == 0 || mss > CC_MSS_MAX) return LVLIP_EINVAL;
+        if (mss == 0 || mss > TCP_MSS_MAX) return LVLIP_EINVAL;
         if (c[k].cwnd < mss || c[k].cwnd > LVLIP_CC_MAX_WND) return LVLIP_EINVAL;
         if (c[k].cwnd_max < mss || c[k].cwnd_max > LVLIP_CC_MAX_WND) return LVLIP_EINVAL;
         if (c[k].ssthresh > LVLIP_CC_MAX_WND || c[k].in_rec > 1u) return LVLIP_EINVAL;
@@ -40,48 +38,13 @@ int lvlip_cc_cpu(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lvl
             res[k].cwnd = x->cwnd, res[k].sacked_bytes = 0, res[k].n_sacked = 0, res[k].event = 0;
             continue;
         }
-        const uint32_t mss = x->mss, nxt = s[k].snd_nxt, una = s[k].snd_una;
-        const uint32_t flight = nxt - una;
-        const uint32_t a = snd ? snd[k].acked : 0u, n_new = snd ? snd[k].n_new : 0u;
-        const uint32_t fired = prev ? prev[k].fired : 0u, bo = prev ? prev[k].backoff : 0u;
-        const uint32_t half = flight / 2u > 2u * mss ? flight / 2u : 2u * mss;
-        uint32_t event = 0;
-        /* 1: loss */
-        if (fired == LVLIP_RTO_TIMEOUT) {
-            if (bo == 1u) x->ssthresh = half;
-            x->cwnd = mss, x->acc = 0, x->in_rec = 0, x->recover = nxt;
-            event |= LVLIP_CC_EV_TIMEOUT;
-        } else if (fired == LVLIP_RTO_FASTRTX && !x->in_rec) {
-            x->ssthresh = half, x->cwnd = half, x->acc = 0, x->in_rec = 1, x->recover = nxt;
-            event |= LVLIP_CC_EV_ENTER;
-        }
-        /* 2: ACKs */
-        if (n_new && a) {
-            uint64_t cwnd = x->cwnd;
-            if (x->in_rec) {
-                if (a >= (uint32_t)(x->recover - una)) {
-                    x->in_rec = 0, x->acc = 0;
-                    cwnd = x->ssthresh;
-                    event |= LVLIP_CC_EV_EXIT;
-                }
-            } else if (cwnd < x->ssthresh) {
-                const uint64_t cap = (uint64_t)n_new * mss;
-                cwnd += a < cap ? a : cap;
-                event |= LVLIP_CC_EV_SLOWSTART;
-            } else {
-                uint64_t acc = (uint64_t)x->acc + a;
-                if (acc >= cwnd) {
-                    acc -= cwnd;
-                    cwnd += mss;
-                    event |= LVLIP_CC_EV_AVOID;
-                }
-                x->acc = (uint32_t)(acc < cwnd ? acc : cwnd);
-            }
-            x->cwnd = (uint32_t)(cwnd < x->cwnd_max ? cwnd : x->cwnd_max);
-        }
+        /* 1: loss, 2: ACKs */
+        const uint32_t event = flow_cc_step(x, s[k].snd_una, s[k].snd_nxt, snd ? snd[k].acked : 0u,
+                                            snd ? snd[k].n_new : 0u, prev ? prev[k].fired : 0u,
+                                            prev ? prev[k].backoff : 0u);
         /* 3: pipe */
-        uint64_t bytes = 0;
-        uint32_t n_sacked = 0;
+        uint64_t sum = 0;
+        uint32_t n_sacked = 0, bytes;
         if (sacked) {
             const uint32_t nseg = s[k].nseg;
             const uint32_t p = snd && snd[k].popped < nseg ? snd[k].popped : snd ? nseg : 0u;
@@ -89,14 +52,12 @@ int lvlip_cc_cpu(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lvl
             for (uint64_t q = (uint64_t)s[k].seg0 + p; q < q1; q++) {
                 if (!sacked[q]) continue;
                 n_sacked++;
-                if (fd[q].len >= CC_HDR) bytes += fd[q].len - CC_HDR;
+                if (fd[q].len >= TCP_FRAME_HDR) sum += fd[q].len - TCP_FRAME_HDR;
             }
-            if (bytes > LVLIP_CC_MAX_WND) bytes = LVLIP_CC_MAX_WND;
         }
         /* 4: output */
-        const uint64_t cap = (uint64_t)x->cwnd + bytes;
-        t[k].wnd_cap = cap < LVLIP_CC_MAX_WND ? (uint32_t)cap : LVLIP_CC_MAX_WND;
-        res[k].cwnd = x->cwnd, res[k].sacked_bytes = (uint32_t)bytes, res[k].n_sacked = n_sacked, res[k].event = event;
+        t[k].wnd_cap = flow_cc_cap(x->cwnd, sum, &bytes);
+        res[k].cwnd = x->cwnd, res[k].sacked_bytes = bytes, res[k].n_sacked = n_sacked, res[k].event = event;
     }
     return LVLIP_OK;
 }

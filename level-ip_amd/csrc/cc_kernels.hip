@@ -18,8 +18,9 @@
 //              into the first 8 bytes of res[k] and one 32-bit add into its
 //              third dword; a wave without a marked entry issues none.  Dead
 //              flows are skipped.  Not launched with a NULL sacked.
-//   k_cc_fin   one lane per flow: steps 1, 2 and 4 on the sums, c[k] (32 B),
-//              res[k] (one 16-B store) and t[k].wnd_cap.
+//   k_cc_fin   one lane per flow: steps 1, 2 and 4 on the sums (flow_step.h,
+//              which cc_cpu.c calls too), c[k] (32 B), res[k] (one 16-B store)
+//              and t[k].wnd_cap.
 //
 // Integer adds are the only reductions, so the bytes do not depend on the run.
 // No LDS, no workspace beyond res, plain C++ and vector stores.
@@ -33,7 +34,7 @@
 
 #include <stdint.h>
 
-#include "lvlip_skb.h"
+#include "flow_step.h"
 #include "tcp_hdr_dev.h"
 #include "wave_ops.h"
 
@@ -44,15 +45,6 @@ constexpr uint32_t CC_Y = 1024;           // most chunks a queue is spread over
 constexpr uint32_t CC_Y_MIN = 8;          // fewest
 constexpr uint32_t CC_GRID = 1u << 17;    // workgroups of k_cc_sum the chunk count aims at
 constexpr int CC_UNROLL = 4;              // chunks of 64 entries a wave has in flight
-constexpr uint32_t CC_HDR = 54u;          // the header of every frame lvlip_tso_* / lvlip_push_* build
-constexpr uint32_t CC_MAX_WND = LVLIP_CC_MAX_WND;
-
-// the sum of the wave's 64 values, in every lane
-__device__ __forceinline__ uint64_t wave_add_u64(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void k_cc_sum(const lvlip_snd_flow* s, const lvlip_snd_result* snd,
                                                 const lvlip_rto_flow* t, uint32_t nflows, const lvlip_frame_desc* fd,
@@ -87,7 +79,8 @@ __global__ __launch_bounds__(256) void k_cc_sum(const lvlip_snd_flow* s, const l
 #pragma unroll
         for (int u = 0; u < CC_UNROLL; ++u) {
             count += mark[u] ? 1u : 0u;
-            bytes += flen[u] >= CC_HDR ? flen[u] - CC_HDR : 0u;
+            // behind TCP_FRAME_HDR, the header of every frame lvlip_tso_* / lvlip_push_* build
+            bytes += flen[u] >= (uint32_t)TCP_FRAME_HDR ? flen[u] - (uint32_t)TCP_FRAME_HDR : 0u;
         }
     }
     count = wave_add_u32(count);
@@ -108,8 +101,6 @@ __global__ __launch_bounds__(256) void k_cc_fin(const lvlip_snd_flow* s, const l
         return;
     }
     const uint4 r = load_global(R);  // the byte sum's halves, n_sacked, 0
-    const uint32_t mss = x.mss, una = s[k].snd_una, nxt = s[k].snd_nxt;
-    const uint32_t flight = nxt - una;
     uint32_t a = 0u, n_new = 0u, fired = 0u, bo = 0u;
     if (snd) {
         const uint4 v = load_global(reinterpret_cast<uint64_t>(snd + k));  // snd_una, acked, n_new, n_dup
@@ -119,48 +110,12 @@ __global__ __launch_bounds__(256) void k_cc_fin(const lvlip_snd_flow* s, const l
         const uint4 v = load_global(reinterpret_cast<uint64_t>(prev + k));  // fired, sample, rto, backoff
         fired = v.x, bo = v.w;
     }
-    const uint32_t half = max(flight / 2u, 2u * mss);
-    uint32_t event = 0u;
-    // 1: loss
-    if (fired == LVLIP_RTO_TIMEOUT) {
-        if (bo == 1u) x.ssthresh = half;
-        x.cwnd = mss, x.acc = 0u, x.in_rec = 0, x.recover = nxt;
-        event |= LVLIP_CC_EV_TIMEOUT;
-    } else if (fired == LVLIP_RTO_FASTRTX && !x.in_rec) {
-        x.ssthresh = half, x.cwnd = half, x.acc = 0u, x.in_rec = 1, x.recover = nxt;
-        event |= LVLIP_CC_EV_ENTER;
-    }
-    // 2: ACKs
-    if (n_new && a) {
-        uint64_t cwnd = x.cwnd;
-        if (x.in_rec) {
-            if (a >= x.recover - una) {
-                x.in_rec = 0, x.acc = 0u;
-                cwnd = x.ssthresh;
-                event |= LVLIP_CC_EV_EXIT;
-            }
-        } else if (cwnd < x.ssthresh) {
-            const uint64_t cap = (uint64_t)n_new * mss;
-            cwnd += a < cap ? a : cap;
-            event |= LVLIP_CC_EV_SLOWSTART;
-        } else {
-            uint64_t acc = (uint64_t)x.acc + a;
-            if (acc >= cwnd) {
-                acc -= cwnd;
-                cwnd += mss;
-                event |= LVLIP_CC_EV_AVOID;
-            }
-            x.acc = (uint32_t)(acc < cwnd ? acc : cwnd);
-        }
-        x.cwnd = (uint32_t)(cwnd < x.cwnd_max ? cwnd : x.cwnd_max);
-    }
-    // 4: output
-    uint64_t bytes = ((uint64_t)r.y << 32) | r.x;
-    if (bytes > CC_MAX_WND) bytes = CC_MAX_WND;
-    const uint64_t cap = (uint64_t)x.cwnd + bytes;
+    const uint32_t event = flow_cc_step(&x, s[k].snd_una, s[k].snd_nxt, a, n_new, fired, bo);  // 1: loss, 2: ACKs
+    uint32_t bytes;
+    const uint32_t cap = flow_cc_cap(x.cwnd, ((uint64_t)r.y << 32) | r.x, &bytes);  // 4: output
     c[k] = x;
-    store_global(R, u32x4{x.cwnd, (uint32_t)bytes, r.z, event});
-    t[k].wnd_cap = cap < CC_MAX_WND ? (uint32_t)cap : CC_MAX_WND;
+    store_global(R, u32x4{x.cwnd, bytes, r.z, event});
+    t[k].wnd_cap = cap;
 }
 
 }  // namespace lvlip
@@ -174,9 +129,7 @@ int lvlip_cc_dev(const lvlip_snd_flow* s, const lvlip_snd_result* snd, const lvl
     if (nflows == 0) return LVLIP_OK;
     if (!s || !c || !t || !res || (sacked && !fd)) return LVLIP_EINVAL;
     if (nflows > LVLIP_LRO_MAX_FLOWS) return LVLIP_EINVAL;
-    if (((uintptr_t)s & 7u) || ((uintptr_t)c & 7u) || ((uintptr_t)t & 7u) || ((uintptr_t)snd & 15u) ||
-        ((uintptr_t)prev & 15u) || ((uintptr_t)fd & 15u) || ((uintptr_t)res & 15u))
-        return LVLIP_EINVAL;
+    if (any_misaligned<8>(s, c, t) || any_misaligned<16>(snd, prev, fd, res)) return LVLIP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     int rc = lvlip_launch_status(hipMemsetAsync(res, 0, (size_t)nflows * sizeof *res, st), "lvlip_cc_dev: memset");
     if (rc != LVLIP_OK) return rc;

@@ -1,0 +1,193 @@
+/*
+ * flow_step.h — one flow's step of the protocol state machines, once for both
+ * sides: the retransmission timer, the congestion window, the peer's window,
+ * the push count and the class of an ACK.  The CPU forms (rto_cpu.c, cc_cpu.c,
+ * push_cpu.c, snd_cpu.c) call these on the flow in the caller's array, the
+ * kernels (rto_, cc_, push_ and snd_kernels.hip) on a flow in registers.
+ * Every function takes scalars and one flow; none sees a batch.  How a flow's
+ * words travel between HBM and registers, which lane runs the step and what is
+ * reduced around it stays in the kernels.  Plain C99, not installed.
+ */
+#ifndef LVLIP_FLOW_STEP_H
+#define LVLIP_FLOW_STEP_H
+
+#include <stdint.h>
+
+#include "lvlip_skb.h"
+
+#ifdef __HIPCC__
+#define FLOW_FN __host__ __device__ __forceinline__
+#else
+#define FLOW_FN static inline
+#endif
+
+#define FLOW_NONE 0xFFFFFFFFu    /* no flow, no queue entry, no sample, no winner; a plan's refusal */
+#define FLOW_WND_MAX 0x40000000u /* the largest window: 0xFFFF << 14 is below it (RFC 7323 2.3) */
+
+#define FLOW_ACK_NEW 0u    /* src/tcp_input.c:330-331: snd_una only ever rises */
+#define FLOW_ACK_DUP 1u
+#define FLOW_ACK_OLD 2u    /* :338 */
+#define FLOW_ACK_BEYOND 3u /* :343 */
+
+/* The fifth check (src/tcp_input.c:311-356) on d = ack_seq - snd_una against
+ * span = snd_nxt - snd_una, both mod 2^32.  The classes are numbered in the
+ * order of lvlip_snd_result's counters (n_new, n_dup, n_old, n_beyond), which
+ * k_snd_rec indexes with them.  A record counts for the window when its class
+ * is at most FLOW_ACK_DUP, which is d <= span. */
+FLOW_FN uint32_t flow_ack_class(uint32_t d, uint32_t span)
+{
+    return d == 0u ? FLOW_ACK_DUP : d <= span ? FLOW_ACK_NEW : d >= 0x80000000u ? FLOW_ACK_OLD : FLOW_ACK_BEYOND;
+}
+
+/* the window field raw of the winning ACK as bytes; the mask is a no-op for a
+ * wscale lvlip_rto_check accepts and keeps the shift defined for any other */
+FLOW_FN uint32_t flow_wnd_scale(uint32_t raw, uint32_t wscale)
+{
+    const uint64_t v = (uint64_t)raw << (wscale & 15u);
+    return v > FLOW_WND_MAX ? FLOW_WND_MAX : (uint32_t)v;
+}
+
+/* LVLIP_WND_APPLY: what the write queue may have in flight */
+FLOW_FN uint32_t flow_wnd_apply(uint32_t snd_wnd, uint32_t wnd_cap) { return snd_wnd < wnd_cap ? snd_wnd : wnd_cap; }
+
+typedef struct flow_rto_out {
+    uint32_t fired;  /* 0, LVLIP_RTO_TIMEOUT or LVLIP_RTO_FASTRTX */
+    uint32_t sample; /* the round-trip sample in ms, FLOW_NONE when none was taken */
+} flow_rto_out;
+
+/* Steps 1-4 of lvlip_rto_* on *x, for a queue of nseg entries of which this
+ * round pushed the last `pushed`, n_new new and n_dup duplicate ACKs, at time
+ * now.  A dead flow is left as it is. */
+FLOW_FN flow_rto_out flow_rto_step(lvlip_rto_flow *x, uint32_t nseg, uint32_t pushed, uint32_t n_new, uint32_t n_dup,
+                                   uint32_t now, uint32_t flags)
+{
+    flow_rto_out o = {0u, FLOW_NONE};
+    if (x->dead) return o;
+    if (pushed > nseg) pushed = nseg;
+    const uint32_t before = nseg - pushed;
+    const uint32_t dup0 = x->dupacks;
+    if (n_new) { /* src/tcp_input.c:330-334: tcp_rtt, then tcp_clean_rto_queue */
+        if (x->backoff == 0 && x->armed) { /* Karn, src/tcp.c:426 */
+            const int32_t r = (int32_t)(now - (x->expires - x->rto));
+            if (r >= 0) {
+                /* tcp_rtt, src/tcp.c:431-451.  The integer forms equal the reference's double arithmetic (include/
+                 * lvlip_skb.h); 64-bit intermediates, so no product overflows whatever state the caller hands in. */
+                o.sample = (uint32_t)r;
+                if (!x->srtt) { /* RFC 6298 2.2 */
+                    x->srtt = r;
+                    x->rttvar = r / 2;
+                } else { /* 2.3 */
+                    const int64_t e = (int64_t)x->srtt - r;
+                    x->rttvar = (int32_t)(uint32_t)(uint64_t)((3 * (int64_t)x->rttvar + (e < 0 ? -e : e)) / 4);
+                    x->srtt = (int32_t)(uint32_t)(uint64_t)((7 * (int64_t)x->srtt + r) / 8);
+                }
+                int64_t k = 4 * (int64_t)x->rttvar;
+                if (k < 200) k = 200; /* :449 */
+                x->rto = (uint32_t)(uint64_t)(x->srtt + k);
+            }
+        }
+        x->dupacks = 0;
+        if (before == 0) x->armed = 0, x->backoff = 0; /* tcp_stop_rto_timer, src/tcp_input.c:86-89 */
+    } else {
+        x->dupacks += n_dup;
+    }
+    if (pushed && before == 0) { /* src/tcp_output.c:138-140 */
+        x->armed = 1;
+        x->expires = now + x->rto;
+    }
+    if (x->armed && x->expires < now) { /* src/timer.c:71 */
+        if (nseg == 0) { /* src/tcp_output.c:371-375 */
+            x->armed = 0, x->backoff = 0;
+        } else {
+            o.fired = LVLIP_RTO_TIMEOUT;
+            if (x->rto > LVLIP_RTO_DEAD_MS) { /* :384-391; tcp_done stops the timer, src/tcp.c:313-334 */
+                x->dead = 1, x->armed = 0, x->backoff = 0;
+            } else { /* :394-396 */
+                x->rto *= 2u;
+                x->backoff++;
+                x->expires = now + x->rto;
+            }
+        }
+    }
+    if ((flags & LVLIP_RTO_FAST) && !o.fired && dup0 < 3u && x->dupacks >= 3u && nseg) o.fired = LVLIP_RTO_FASTRTX;
+    return o;
+}
+
+/* Steps 1 and 2 of lvlip_cc_* on *x of a live flow: the cut after the loss the
+ * last lvlip_rto_* call reported (fired, backoff), then the round's n_new new
+ * ACKs for `acked` bytes.  Returns the LVLIP_CC_EV_* bits. */
+FLOW_FN uint32_t flow_cc_step(lvlip_cc_flow *x, uint32_t una, uint32_t nxt, uint32_t acked, uint32_t n_new,
+                              uint32_t fired, uint32_t backoff)
+{
+    const uint32_t mss = x->mss, flight = nxt - una;
+    const uint32_t half = flight / 2u > 2u * mss ? flight / 2u : 2u * mss;
+    uint32_t event = 0;
+    /* 1: loss */
+    if (fired == LVLIP_RTO_TIMEOUT) {
+        if (backoff == 1u) x->ssthresh = half;
+        x->cwnd = mss, x->acc = 0, x->in_rec = 0, x->recover = nxt;
+        event |= LVLIP_CC_EV_TIMEOUT;
+    } else if (fired == LVLIP_RTO_FASTRTX && !x->in_rec) {
+        x->ssthresh = half, x->cwnd = half, x->acc = 0, x->in_rec = 1, x->recover = nxt;
+        event |= LVLIP_CC_EV_ENTER;
+    }
+    /* 2: ACKs */
+    if (n_new && acked) {
+        uint64_t cwnd = x->cwnd;
+        if (x->in_rec) {
+            if (acked >= (uint32_t)(x->recover - una)) {
+                x->in_rec = 0, x->acc = 0;
+                cwnd = x->ssthresh;
+                event |= LVLIP_CC_EV_EXIT;
+            }
+        } else if (cwnd < x->ssthresh) {
+            const uint64_t cap = (uint64_t)n_new * mss;
+            cwnd += acked < cap ? acked : cap;
+            event |= LVLIP_CC_EV_SLOWSTART;
+        } else {
+            uint64_t acc = (uint64_t)x->acc + acked;
+            if (acc >= cwnd) {
+                acc -= cwnd;
+                cwnd += mss;
+                event |= LVLIP_CC_EV_AVOID;
+            }
+            x->acc = (uint32_t)(acc < cwnd ? acc : cwnd);
+        }
+        x->cwnd = (uint32_t)(cwnd < x->cwnd_max ? cwnd : x->cwnd_max);
+    }
+    return event;
+}
+
+/* Step 4: wnd_cap from cwnd and the pipe sum of step 3; *bytes gets the sum as
+ * the result reports it.  Both stop at LVLIP_CC_MAX_WND. */
+FLOW_FN uint32_t flow_cc_cap(uint32_t cwnd, uint64_t sum, uint32_t *bytes)
+{
+    *bytes = sum < LVLIP_CC_MAX_WND ? (uint32_t)sum : LVLIP_CC_MAX_WND;
+    const uint64_t cap = (uint64_t)cwnd + *bytes;
+    return cap < LVLIP_CC_MAX_WND ? (uint32_t)cap : LVLIP_CC_MAX_WND;
+}
+
+/* Step 2 of lvlip_push_*: the segments flow *w may append now to the queue *s,
+ * and their payload bytes.  The device cannot refuse its input, so a zero mss
+ * and a queue that is not the plan's (longer than cap, or below q0) push
+ * nothing.  For a flow lvlip_push_plan accepted, whose queue step 1 has moved
+ * to q0 or will, these guards always hold: mss > 0, nseg <= cap and
+ * seg0 >= q0. */
+FLOW_FN uint32_t flow_push_count(const lvlip_push_flow *w, const lvlip_snd_flow *s, uint32_t *bytes)
+{
+    const uint32_t unsent = w->unsent, mss = w->mss, wnd = w->wnd, push = w->push;
+    const uint32_t span = s->snd_nxt - s->snd_una;
+    const uint32_t need = mss ? (uint32_t)(((uint64_t)unsent + mss - 1u) / mss) : 0u;
+    uint32_t m = s->nseg < w->cap && (s->seg0 >= w->q0 || s->nseg == 0u) ? w->cap - s->nseg : 0u;
+    if (push < m) m = push;
+    if (need < m) m = need;
+    /* span + min(m*mss, unsent) <= wnd: everything that is ready fits, or whole segments of the room */
+    const uint32_t room = span <= wnd ? wnd - span : 0u;
+    const uint32_t fit = span <= wnd && unsent <= room ? need : (mss ? room / mss : 0u);
+    if (fit < m) m = fit;
+    const uint64_t b = (uint64_t)m * mss;
+    *bytes = b < unsent ? (uint32_t)b : unsent;
+    return m;
+}
+
+#endif

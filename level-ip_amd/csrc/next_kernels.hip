@@ -21,7 +21,7 @@
 #include <stdint.h>
 
 #include "lvlip_skb.h"
-#include "tcp_hdr_dev.h"  // lvlip_launched
+#include "tcp_hdr_dev.h"  // lvlip_launched, any_misaligned
 
 namespace lvlip {
 
@@ -67,7 +67,7 @@ extern "C" {
 int lvlip_lro_next_dev(lvlip_lro_flow* f, lvlip_lro_result* res, uint32_t nflows, void* stream) {
     if (nflows == 0) return LVLIP_OK;
     if (!f || !res || nflows > LVLIP_LRO_MAX_FLOWS) return LVLIP_EINVAL;
-    if (((uintptr_t)f & 7u) || ((uintptr_t)res & 15u)) return LVLIP_EINVAL;
+    if (any_misaligned<8>(f) || any_misaligned<16>(res)) return LVLIP_EINVAL;
     hipLaunchKernelGGL(lvlip::k_lro_next, dim3((nflows + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, f, res,
                        nflows);
     return lvlip_launched("k_lro_next");
@@ -76,7 +76,7 @@ int lvlip_lro_next_dev(lvlip_lro_flow* f, lvlip_lro_result* res, uint32_t nflows
 int lvlip_snd_next_dev(lvlip_snd_flow* s, lvlip_snd_result* res, uint32_t nflows, void* stream) {
     if (nflows == 0) return LVLIP_OK;
     if (!s || !res || nflows > LVLIP_LRO_MAX_FLOWS) return LVLIP_EINVAL;
-    if (((uintptr_t)s & 7u) || ((uintptr_t)res & 15u)) return LVLIP_EINVAL;
+    if (any_misaligned<8>(s) || any_misaligned<16>(res)) return LVLIP_EINVAL;
     hipLaunchKernelGGL(lvlip::k_snd_next, dim3((nflows + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, s, res,
                        nflows);
     return lvlip_launched("k_snd_next");

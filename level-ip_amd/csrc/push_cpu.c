@@ -8,9 +8,9 @@
  * round's worth of every flow's ready bytes becomes frames in the flow's slots
  * of the TX ring, through tcp_seg_write, the frame writer lvlip_tso_cpu uses.
  */
+#include "flow_step.h"
 #include "tcp_hdr.h"
 
-#define NONE 0xFFFFFFFFu
 #define PUSH_MAX_BYTES 0x40000000u
 #define TCP_NO_PUSH_FLAGS 0x27u /* byte 13 of the TCP header: FIN 0x01, SYN 0x02, RST 0x04, URG 0x20 */
 
@@ -35,22 +35,22 @@ uint32_t lvlip_push_plan(lvlip_push_flow *w, const lvlip_snd_flow *s, uint32_t n
     if (ring_bytes) *ring_bytes = 0;
     if (nfd) *nfd = 0;
     if (nflows == 0) return 0;
-    if (!w || !s || nflows > LVLIP_LRO_MAX_FLOWS) return NONE;
+    if (!w || !s || nflows > LVLIP_LRO_MAX_FLOWS) return FLOW_NONE;
     uint64_t slots = 0, caps = 0, top = 0;
     uint32_t topq = 0;
     for (uint32_t k = 0; k < nflows; k++) {
-        if (!flow_ok(&w[k], &s[k])) return NONE;
+        if (!flow_ok(&w[k], &s[k])) return FLOW_NONE;
         slots += w[k].push;
         caps += w[k].cap;
         const uint64_t end = w[k].ring_off + (uint64_t)(w[k].cap - 1u) * w[k].stride + TCP_FRAME_HDR + w[k].mss;
         if (end > top) top = end;
         if (w[k].q0 + w[k].cap > topq) topq = w[k].q0 + w[k].cap;
     }
-    if (slots > LVLIP_MAX_BATCH || caps > LVLIP_MAX_BATCH) return NONE;
+    if (slots > LVLIP_MAX_BATCH || caps > LVLIP_MAX_BATCH) return FLOW_NONE;
     /* no two fd regions and no two ring ranges may share an element */
     if (nflows > 1u) {
         uint64_t *r = malloc((size_t)nflows * 2u * sizeof *r);
-        if (!r) return NONE;
+        if (!r) return FLOW_NONE;
         for (uint32_t k = 0; k < nflows; k++) {
             r[2u * k] = w[k].q0;
             r[2u * k + 1u] = (uint64_t)w[k].q0 + w[k].cap;
@@ -62,7 +62,7 @@ uint32_t lvlip_push_plan(lvlip_push_flow *w, const lvlip_snd_flow *s, uint32_t n
         }
         ok = ok && ranges_disjoint(r, nflows);
         free(r);
-        if (!ok) return NONE;
+        if (!ok) return FLOW_NONE;
     }
     uint32_t slot = 0;
     for (uint32_t k = 0; k < nflows; k++) {
@@ -72,23 +72,6 @@ uint32_t lvlip_push_plan(lvlip_push_flow *w, const lvlip_snd_flow *s, uint32_t n
     if (ring_bytes) *ring_bytes = top;
     if (nfd) *nfd = topq;
     return slot;
-}
-
-/* step 2: the segments flow k may append now, and their payload bytes */
-static uint32_t push_count(const lvlip_push_flow *w, const lvlip_snd_flow *s, uint32_t *bytes)
-{
-    const uint32_t span = s->snd_nxt - s->snd_una;
-    const uint32_t need = (uint32_t)(((uint64_t)w->unsent + w->mss - 1u) / w->mss);
-    uint32_t m = s->nseg < w->cap ? w->cap - s->nseg : 0u;
-    if (w->push < m) m = w->push;
-    if (need < m) m = need;
-    /* span + min(m*mss, unsent) <= wnd: everything that is ready fits, or whole segments of the room */
-    const uint32_t room = span <= w->wnd ? w->wnd - span : 0u;
-    const uint32_t fit = w->unsent <= room && span <= w->wnd ? need : room / w->mss;
-    if (fit < m) m = fit;
-    const uint64_t b = (uint64_t)m * w->mss;
-    *bytes = b < w->unsent ? (uint32_t)b : w->unsent;
-    return m;
 }
 
 int lvlip_push_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, lvlip_snd_flow *s, lvlip_push_flow *w,
@@ -117,9 +100,9 @@ int lvlip_push_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, lvlip_s
             q->seg0 = t->q0;
             moved = q->nseg;
         }
-        /* 2 */
+        /* 2: the count */
         uint32_t bytes;
-        const uint32_t m = push_count(t, q, &bytes);
+        const uint32_t m = flow_push_count(t, q, &bytes);
         /* 3: the template as tcp_transmit_skb would fill it now (src/tcp_output.c:107-109) */
         uint8_t hdr[TCP_FRAME_HDR];
         memcpy(hdr, t->hdr, sizeof hdr);

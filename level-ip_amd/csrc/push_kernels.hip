@@ -10,8 +10,9 @@
 //                 step loads all of its entries before it stores one (the
 //                 stores take the loads' data), and its stores end below the
 //                 next step's loads because q0 < seg0: memmove's result
-//                 whatever the distance.  Step 2: lane 0 counts m and writes
-//                 res and seg0.
+//                 whatever the distance.  Step 2: lane 0 counts m
+//                 (flow_step.h, which push_cpu.c calls too) and writes res
+//                 and seg0.
 //   k_push        k_tso's mapping and k_tso's row (seg_frame_dev.h): one DPP
 //                 row per slot, four slots per wave; slot g -> flow by a binary
 //                 search over the flows' slot0 (lvlip_push_plan's running sum);
@@ -32,6 +33,7 @@
 
 #include <stdint.h>
 
+#include "flow_step.h"
 #include "seg_frame_dev.h"
 
 namespace lvlip {
@@ -69,17 +71,14 @@ __global__ __launch_bounds__(256) void k_push_count(lvlip_snd_flow* s, const lvl
 
     // ---- 2: the count
     if (lane == 0u) {
-        const uint32_t unsent = t->unsent, mss = t->mss, wnd = t->wnd;
-        const uint32_t span = nxt - una;
-        const uint32_t need = mss ? (uint32_t)(((uint64_t)unsent + mss - 1u) / mss) : 0u;
-        uint32_t m = nseg < cap && (seg0 >= q0 || nseg == 0u) ? cap - nseg : 0u;
-        m = min(m, min(t->push, need));
-        const bool open = span <= wnd;
-        const uint32_t room = open ? wnd - span : 0u;
-        const uint32_t fit = open && unsent <= room ? need : (mss ? room / mss : 0u);
-        m = min(m, fit);
-        const uint64_t by = (uint64_t)m * mss;
-        const uint32_t bytes = by < unsent ? (uint32_t)by : unsent;
+        // register copies of the words the count reads: the queue where step 1 found it (flow_push_count
+        // refuses one below q0), and of w[k] the four words not loaded yet
+        lvlip_snd_flow q = {};
+        q.snd_una = una, q.snd_nxt = nxt, q.seg0 = seg0, q.nseg = nseg;
+        lvlip_push_flow p = {};
+        p.q0 = q0, p.cap = cap, p.unsent = t->unsent, p.mss = t->mss, p.wnd = t->wnd, p.push = t->push;
+        uint32_t bytes;
+        const uint32_t m = flow_push_count(&p, &q, &bytes);
         store_global(reinterpret_cast<uint64_t>(res + k), u32x4{m, bytes, q0 + nseg, moved});
         s[k].seg0 = q0;
     }
@@ -168,9 +167,7 @@ int lvlip_push_dev(const lvlip_lro_flow* f, const lvlip_lro_result* lro, lvlip_s
     if (nslots && (!payload || !base || !fd_out || nflows == 0)) return LVLIP_EINVAL;
     if (nflows == 0) return LVLIP_OK;
     if (!f || !s || !w || !fd || !res) return LVLIP_EINVAL;
-    if (((uintptr_t)f & 7u) || ((uintptr_t)s & 7u) || ((uintptr_t)w & 7u) || ((uintptr_t)lro & 15u) ||
-        ((uintptr_t)fd & 15u) || ((uintptr_t)fd_out & 15u) || ((uintptr_t)res & 15u))
-        return LVLIP_EINVAL;
+    if (any_misaligned<8>(f, s, w) || any_misaligned<16>(lro, fd, fd_out, res)) return LVLIP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t fgrid = (nflows + lvlip::PUSH_WAVES - 1u) / lvlip::PUSH_WAVES;
     hipLaunchKernelGGL(lvlip::k_push_count, dim3(fgrid), dim3(256), 0, st, s, w, nflows, fd, sacked, res);

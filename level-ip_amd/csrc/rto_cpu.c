@@ -10,10 +10,8 @@
  * (src/tcp_input.c:86-89), once per flow and round; lvlip_wnd_cpu reads the
  * window field the reference leaves as a TODO (src/tcp_input.c:352-354).
  */
+#include "flow_step.h"
 #include "tcp_hdr.h"
-
-#define NONE 0xFFFFFFFFu
-#define WND_MAX 0x40000000u
 
 int lvlip_rto_check(const lvlip_rto_flow *t, uint32_t nflows)
 {
@@ -21,7 +19,7 @@ int lvlip_rto_check(const lvlip_rto_flow *t, uint32_t nflows)
     if (!t || nflows > LVLIP_LRO_MAX_FLOWS) return LVLIP_EINVAL;
     for (uint32_t k = 0; k < nflows; k++) {
         if (t[k].wscale > LVLIP_WSCALE_MAX || t[k].armed > 1u || t[k].dead > 1u) return LVLIP_EINVAL;
-        if (t[k].snd_wnd > WND_MAX || t[k].wnd_cap > WND_MAX) return LVLIP_EINVAL;
+        if (t[k].snd_wnd > FLOW_WND_MAX || t[k].wnd_cap > FLOW_WND_MAX) return LVLIP_EINVAL;
     }
     return LVLIP_OK;
 }
@@ -54,10 +52,10 @@ int lvlip_wnd_cpu(const lvlip_lro_flow *f, const lvlip_snd_flow *s, lvlip_rto_fl
     /* res[k].raw holds the winner's d + 1 until the flows are finished */
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t k = rec_ack_flow(&rec[i], f, nflows);
-        if (k == NONE) continue;
+        if (k == FLOW_NONE) continue;
         const uint32_t d = rec[i].ack_seq - s[k].snd_una;
         uint32_t raw;
-        if (d > (uint32_t)(s[k].snd_nxt - s[k].snd_una)) continue; /* old or beyond */
+        if (flow_ack_class(d, s[k].snd_nxt - s[k].snd_una) > FLOW_ACK_DUP) continue; /* old or beyond */
         if (!wnd_frame((const uint8_t *)ack_base + ack_fd[i].offset, ack_fd[i].len, &raw)) continue;
         res[k].n_counting++;
         if (d + 1u >= res[k].raw) { /* i ascends: the later record among equals */
@@ -68,37 +66,18 @@ int lvlip_wnd_cpu(const lvlip_lro_flow *f, const lvlip_snd_flow *s, lvlip_rto_fl
     }
     for (uint32_t k = 0; k < nflows; k++) {
         if (res[k].raw) {
-            const uint64_t v = (uint64_t)res[k].snd_wnd << t[k].wscale;
             res[k].raw = res[k].snd_wnd;
-            t[k].snd_wnd = v > WND_MAX ? WND_MAX : (uint32_t)v;
+            t[k].snd_wnd = flow_wnd_scale(res[k].raw, t[k].wscale);
         } else {
-            res[k].winner = NONE;
+            res[k].winner = FLOW_NONE;
         }
         res[k].snd_wnd = t[k].snd_wnd;
-        if ((flags & LVLIP_WND_APPLY) && w) w[k].wnd = t[k].snd_wnd < t[k].wnd_cap ? t[k].snd_wnd : t[k].wnd_cap;
+        if ((flags & LVLIP_WND_APPLY) && w) w[k].wnd = flow_wnd_apply(t[k].snd_wnd, t[k].wnd_cap);
     }
     return LVLIP_OK;
 }
 
 /* ----------------------------------------------------------------- timer -- */
-
-/* tcp_rtt, src/tcp.c:431-451, for a sample r >= 0.  The integer forms equal the
- * reference's double arithmetic (include/lvlip_skb.h); 64-bit intermediates,
- * so no product overflows whatever state the caller hands in. */
-static void rtt_sample(lvlip_rto_flow *t, int32_t r)
-{
-    if (!t->srtt) { /* RFC 6298 2.2 */
-        t->srtt = r;
-        t->rttvar = r / 2;
-    } else { /* 2.3 */
-        const int64_t e = (int64_t)t->srtt - r;
-        t->rttvar = (int32_t)(uint32_t)(uint64_t)((3 * (int64_t)t->rttvar + (e < 0 ? -e : e)) / 4);
-        t->srtt = (int32_t)(uint32_t)(uint64_t)((7 * (int64_t)t->srtt + r) / 8);
-    }
-    int64_t k = 4 * (int64_t)t->rttvar;
-    if (k < 200) k = 200; /* :449 */
-    t->rto = (uint32_t)(uint64_t)(t->srtt + k);
-}
 
 int lvlip_rto_cpu(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lvlip_push_result *push,
                   lvlip_rto_flow *t, uint32_t nflows, uint32_t now, uint32_t flags, uint8_t *sacked,
@@ -110,51 +89,12 @@ int lvlip_rto_cpu(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lv
     if (lvlip_rto_check(t, nflows) != LVLIP_OK) return LVLIP_EINVAL;
     memset(gate, 0, (size_t)nflows * sizeof *gate);
     for (uint32_t k = 0; k < nflows; k++) {
-        lvlip_rto_flow *x = &t[k];
         const uint32_t nseg = s[k].nseg;
-        uint32_t pushed = push ? push[k].pushed : 0u;
-        if (pushed > nseg) pushed = nseg;
-        const uint32_t before = nseg - pushed;
-        const uint32_t n_new = snd ? snd[k].n_new : 0u, n_dup = snd ? snd[k].n_dup : 0u;
-        const uint32_t dup0 = x->dupacks;
-        uint32_t fired = 0, sample = NONE;
-        if (!x->dead) {
-            if (n_new) { /* src/tcp_input.c:330-334: tcp_rtt, then tcp_clean_rto_queue */
-                if (x->backoff == 0 && x->armed) { /* Karn, src/tcp.c:426 */
-                    const int32_t r = (int32_t)(now - (x->expires - x->rto));
-                    if (r >= 0) {
-                        sample = (uint32_t)r;
-                        rtt_sample(x, r);
-                    }
-                }
-                x->dupacks = 0;
-                if (before == 0) x->armed = 0, x->backoff = 0; /* tcp_stop_rto_timer */
-            } else {
-                x->dupacks += n_dup;
-            }
-            if (pushed && before == 0) { /* src/tcp_output.c:138-140 */
-                x->armed = 1;
-                x->expires = now + x->rto;
-            }
-            if (x->armed && x->expires < now) { /* src/timer.c:71 */
-                if (nseg == 0) { /* src/tcp_output.c:371-375 */
-                    x->armed = 0, x->backoff = 0;
-                } else {
-                    fired = LVLIP_RTO_TIMEOUT;
-                    if (x->rto > LVLIP_RTO_DEAD_MS) { /* :384-391; tcp_done stops the timer, src/tcp.c:313-334 */
-                        x->dead = 1, x->armed = 0, x->backoff = 0;
-                    } else { /* :394-396 */
-                        x->rto *= 2u;
-                        x->backoff++;
-                        x->expires = now + x->rto;
-                    }
-                }
-            }
-            if ((flags & LVLIP_RTO_FAST) && !fired && dup0 < 3u && x->dupacks >= 3u && nseg) fired = LVLIP_RTO_FASTRTX;
-        }
-        res[k].fired = fired, res[k].sample = sample, res[k].rto = x->rto, res[k].backoff = x->backoff;
-        gate[k].popped = fired ? 0u : nseg;
-        if (fired == LVLIP_RTO_TIMEOUT && sacked && nseg) memset(sacked + s[k].seg0, 0, nseg);
+        const flow_rto_out o = flow_rto_step(&t[k], nseg, push ? push[k].pushed : 0u, snd ? snd[k].n_new : 0u,
+                                             snd ? snd[k].n_dup : 0u, now, flags);
+        res[k].fired = o.fired, res[k].sample = o.sample, res[k].rto = t[k].rto, res[k].backoff = t[k].backoff;
+        gate[k].popped = o.fired ? 0u : nseg;
+        if (o.fired == LVLIP_RTO_TIMEOUT && sacked && nseg) memset(sacked + s[k].seg0, 0, nseg);
     }
     return LVLIP_OK;
 }

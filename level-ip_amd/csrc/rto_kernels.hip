@@ -30,6 +30,9 @@
 // shuffle, and a flow that timed out has its scoreboard range cleared 64 bytes
 // a step, a byte per lane, inside [seg0, seg0 + nseg) only.
 //
+// The arithmetic per flow (the ACK class, the window's scale and ceiling, the
+// timer's steps 1-4) is flow_step.h's, which rto_cpu.c calls too.
+//
 // No LDS, no workspace, plain C++ stores; no atomics in k_wnd_fin and k_rto.
 //
 // Bounds.  Flow indices come from rec_ack_flow (below nflows); a frame is read
@@ -43,25 +46,14 @@
 #include <stdint.h>
 
 #include "csum_dev.h"
+#include "flow_step.h"
 #include "tcp_hdr_dev.h"
 #include "wave_ops.h"
 
 namespace lvlip {
 
-constexpr uint32_t RTO_NONE = 0xFFFFFFFFu;
 constexpr int RTO_PEEL = 4;                      // SND_PEEL: flows a wave reduces before lanes go alone
 constexpr uint32_t RTO_WAVES = 4;                // flows per workgroup of k_rto
-constexpr uint32_t WND_MAX = 0x40000000u;
-
-// the maximum of the wave's 64 values, in every lane
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t o = __shfl_xor(v, off, 64);
-        v = v > o ? v : o;
-    }
-    return v;
-}
 
 // The frame test of lvlip_sack_* on the frame at F of len bytes.  *tw gets the
 // dword at 14 + ihl*4 + 12: hl in bits 4-7, the window in the upper half.
@@ -86,15 +78,15 @@ __global__ __launch_bounds__(256) void k_wnd_rec(const lvlip_lro_flow* f, const 
                                                  const lvlip_frame_desc* ack_fd, uint32_t n, lvlip_wnd_result* res) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    uint32_t flow = RTO_NONE;
+    uint32_t flow = FLOW_NONE;
     uint64_t key = 0;  // 0: the record does not count
     if (i < n) {
         const uint4 r = load_global(reinterpret_cast<uint64_t>(rec + i));  // flow, rel, dlen | status | flags, ack_seq
         flow = rec_ack_flow(r, f, nflows);
-        if (flow != RTO_NONE) {
+        if (flow != FLOW_NONE) {
             const uint32_t una = s[flow].snd_una, span = s[flow].snd_nxt - una;
             const uint32_t d = r.w - una;
-            if (d <= span) {  // new or duplicate
+            if (flow_ack_class(d, span) <= FLOW_ACK_DUP) {  // new or duplicate
                 const uint4 fd = load_global(reinterpret_cast<uint64_t>(ack_fd + i));  // offset lo, hi, len, -
                 const uint64_t F = reinterpret_cast<uint64_t>(ack_base) + (((uint64_t)fd.y << 32) | fd.x);
                 uint32_t tw;
@@ -121,7 +113,7 @@ __global__ __launch_bounds__(256) void k_wnd_fin(lvlip_rto_flow* t, lvlip_push_f
     if (k64 >= nflows) return;
     const uint32_t k = (uint32_t)k64;
     const uint4 a = load_global(reinterpret_cast<uint64_t>(res + k));  // winner, d + 1, count, 0
-    uint32_t winner = RTO_NONE, raw = 0u, wnd = t[k].snd_wnd;
+    uint32_t winner = FLOW_NONE, raw = 0u, wnd = t[k].snd_wnd;
     if (a.y) {
         const uint4 fd = load_global(reinterpret_cast<uint64_t>(ack_fd + a.x));
         const uint64_t F = reinterpret_cast<uint64_t>(ack_base) + (((uint64_t)fd.y << 32) | fd.x);
@@ -129,13 +121,12 @@ __global__ __launch_bounds__(256) void k_wnd_fin(lvlip_rto_flow* t, lvlip_push_f
         if (wnd_frame(F, fd.z, &tw)) {  // it passed in k_wnd_rec: the same bytes
             winner = a.x;
             raw = bswap16u(tw >> 16);
-            const uint64_t v = (uint64_t)raw << (t[k].wscale & 15u);
-            wnd = v > WND_MAX ? WND_MAX : (uint32_t)v;
+            wnd = flow_wnd_scale(raw, t[k].wscale);
             t[k].snd_wnd = wnd;
         }
     }
     store_global(reinterpret_cast<uint64_t>(res + k), u32x4{a.z, winner, raw, wnd});
-    if ((flags & LVLIP_WND_APPLY) && w) w[k].wnd = min(wnd, t[k].wnd_cap);
+    if ((flags & LVLIP_WND_APPLY) && w) w[k].wnd = flow_wnd_apply(wnd, t[k].wnd_cap);
 }
 
 // --------------------------------------------------------------- the timer --
@@ -152,58 +143,12 @@ __global__ __launch_bounds__(256) void k_rto(const lvlip_snd_flow* s, const lvli
     uint32_t fired = 0u;
     if (lane == 0u) {
         lvlip_rto_flow x = t[k];
-        uint32_t pushed = push ? push[k].pushed : 0u;
-        pushed = min(pushed, nseg);
-        const uint32_t before = nseg - pushed;
-        const uint32_t n_new = snd ? snd[k].n_new : 0u, n_dup = snd ? snd[k].n_dup : 0u;
-        const uint32_t dup0 = x.dupacks;
-        uint32_t sample = RTO_NONE;
-        if (!x.dead) {
-            if (n_new) {  // src/tcp_input.c:330-334: tcp_rtt, then tcp_clean_rto_queue
-                if (x.backoff == 0 && x.armed) {  // Karn, src/tcp.c:426
-                    const int32_t r = (int32_t)(now - (x.expires - x.rto));
-                    if (r >= 0) {
-                        sample = (uint32_t)r;
-                        if (!x.srtt) {  // RFC 6298 2.2
-                            x.srtt = r;
-                            x.rttvar = r / 2;
-                        } else {  // 2.3
-                            const int64_t e = (int64_t)x.srtt - r;
-                            x.rttvar = (int32_t)(uint32_t)(uint64_t)((3 * (int64_t)x.rttvar + (e < 0 ? -e : e)) / 4);
-                            x.srtt = (int32_t)(uint32_t)(uint64_t)((7 * (int64_t)x.srtt + r) / 8);
-                        }
-                        int64_t kk = 4 * (int64_t)x.rttvar;
-                        if (kk < 200) kk = 200;  // :449
-                        x.rto = (uint32_t)(uint64_t)(x.srtt + kk);
-                    }
-                }
-                x.dupacks = 0u;
-                if (before == 0u) x.armed = 0, x.backoff = 0;  // tcp_stop_rto_timer
-            } else {
-                x.dupacks += n_dup;
-            }
-            if (pushed && before == 0u) {  // src/tcp_output.c:138-140
-                x.armed = 1;
-                x.expires = now + x.rto;
-            }
-            if (x.armed && x.expires < now) {  // src/timer.c:71
-                if (nseg == 0u) {  // src/tcp_output.c:371-375
-                    x.armed = 0, x.backoff = 0;
-                } else {
-                    fired = LVLIP_RTO_TIMEOUT;
-                    if (x.rto > LVLIP_RTO_DEAD_MS) {  // :384-391; tcp_done stops the timer, src/tcp.c:313-334
-                        x.dead = 1, x.armed = 0, x.backoff = 0;
-                    } else {  // :394-396
-                        x.rto *= 2u;
-                        x.backoff++;
-                        x.expires = now + x.rto;
-                    }
-                }
-            }
-            if ((flags & LVLIP_RTO_FAST) && !fired && dup0 < 3u && x.dupacks >= 3u && nseg) fired = LVLIP_RTO_FASTRTX;
-            t[k] = x;
-        }
-        store_global(reinterpret_cast<uint64_t>(res + k), u32x4{fired, sample, x.rto, (uint32_t)x.backoff});
+        const bool live = !x.dead;  // a dead flow's state is not stored
+        const flow_rto_out o = flow_rto_step(&x, nseg, push ? push[k].pushed : 0u, snd ? snd[k].n_new : 0u,
+                                             snd ? snd[k].n_dup : 0u, now, flags);
+        fired = o.fired;
+        if (live) t[k] = x;
+        store_global(reinterpret_cast<uint64_t>(res + k), u32x4{fired, o.sample, x.rto, (uint32_t)x.backoff});
         const uint64_t g = reinterpret_cast<uint64_t>(gate + k);
         store_global(g, u32x4{0u, 0u, 0u, 0u});                            // snd_una acked n_new n_dup
         store_global(g + 16u, u32x4{0u, 0u, fired ? 0u : nseg, 0u});       // n_old n_beyond popped inflight
@@ -227,9 +172,7 @@ int lvlip_wnd_dev(const lvlip_lro_flow* f, const lvlip_snd_flow* s, lvlip_rto_fl
     if (nflows == 0) return LVLIP_OK;
     if (!f || !s || !t || !res || (n && (!rec || !ack_base || !ack_fd))) return LVLIP_EINVAL;
     if (n > LVLIP_MAX_BATCH || nflows > LVLIP_LRO_MAX_FLOWS || (flags & ~LVLIP_WND_APPLY)) return LVLIP_EINVAL;
-    if (((uintptr_t)f & 7u) || ((uintptr_t)s & 7u) || ((uintptr_t)t & 7u) || ((uintptr_t)w & 7u) ||
-        ((uintptr_t)rec & 15u) || ((uintptr_t)ack_fd & 15u) || ((uintptr_t)res & 15u))
-        return LVLIP_EINVAL;
+    if (any_misaligned<8>(f, s, t, w) || any_misaligned<16>(rec, ack_fd, res)) return LVLIP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     int rc = lvlip_launch_status(hipMemsetAsync(res, 0, (size_t)nflows * sizeof *res, st), "lvlip_wnd_dev: memset");
     if (rc != LVLIP_OK) return rc;
@@ -252,9 +195,7 @@ int lvlip_rto_dev(const lvlip_snd_flow* s, const lvlip_snd_result* snd, const lv
     if (nflows == 0) return LVLIP_OK;
     if (!s || !t || !gate || !res) return LVLIP_EINVAL;
     if (nflows > LVLIP_LRO_MAX_FLOWS || (flags & ~LVLIP_RTO_FAST)) return LVLIP_EINVAL;
-    if (((uintptr_t)s & 7u) || ((uintptr_t)t & 7u) || ((uintptr_t)snd & 15u) || ((uintptr_t)push & 15u) ||
-        ((uintptr_t)gate & 15u) || ((uintptr_t)res & 15u))
-        return LVLIP_EINVAL;
+    if (any_misaligned<8>(s, t) || any_misaligned<16>(snd, push, gate, res)) return LVLIP_EINVAL;
     const uint32_t grid = (nflows + lvlip::RTO_WAVES - 1u) / lvlip::RTO_WAVES;
     hipLaunchKernelGGL(lvlip::k_rto, dim3(grid), dim3(256), 0, (hipStream_t)stream, s, snd, push, t, nflows, now, flags,
                        sacked, gate, res);

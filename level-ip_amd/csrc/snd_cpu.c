@@ -10,10 +10,10 @@
  * and tcp_send_next (:198-225) do to a queued segment: tcp_transmit_skb
  * (:93-129) writes ack_seq and the window again and sums the whole segment.
  */
+#include "flow_step.h"
 #include "tcp_hdr.h"
 
 #define SND_HDR TCP_FRAME_HDR
-#define NONE 0xFFFFFFFFu
 
 /* ------------------------------------------------------------------ plan -- */
 
@@ -21,13 +21,13 @@ uint32_t lvlip_snd_plan(lvlip_snd_flow *s, uint32_t nflows, uint32_t *nfd)
 {
     if (nfd) *nfd = 0;
     if (nflows == 0) return 0;
-    if (!s || nflows > LVLIP_LRO_MAX_FLOWS) return NONE;
+    if (!s || nflows > LVLIP_LRO_MAX_FLOWS) return FLOW_NONE;
     uint64_t segs = 0, slots = 0;
     uint32_t top = 0, queues = 0;
     for (uint32_t k = 0; k < nflows; k++) {
-        if (s[k].reserved != 0 || s[k].reserved2 != 0) return NONE;
-        if ((uint32_t)(s[k].snd_nxt - s[k].snd_una) > 0x40000000u) return NONE;
-        if ((uint64_t)s[k].seg0 + s[k].nseg > 0xFFFFFFFFull) return NONE;
+        if (s[k].reserved != 0 || s[k].reserved2 != 0) return FLOW_NONE;
+        if ((uint32_t)(s[k].snd_nxt - s[k].snd_una) > 0x40000000u) return FLOW_NONE;
+        if ((uint64_t)s[k].seg0 + s[k].nseg > 0xFFFFFFFFull) return FLOW_NONE;
         segs += s[k].nseg;
         slots += s[k].rtx;
         if (s[k].nseg) {
@@ -35,11 +35,11 @@ uint32_t lvlip_snd_plan(lvlip_snd_flow *s, uint32_t nflows, uint32_t *nfd)
             if (s[k].seg0 + s[k].nseg > top) top = s[k].seg0 + s[k].nseg;
         }
     }
-    if (segs > LVLIP_MAX_BATCH || slots > LVLIP_MAX_BATCH) return NONE;
+    if (segs > LVLIP_MAX_BATCH || slots > LVLIP_MAX_BATCH) return FLOW_NONE;
     /* no two queues [seg0, seg0 + nseg) that hold an entry may overlap */
     if (queues > 1u) {
         uint64_t *r = malloc((size_t)queues * 2u * sizeof *r);
-        if (!r) return NONE;
+        if (!r) return FLOW_NONE;
         uint32_t m = 0;
         for (uint32_t k = 0; k < nflows; k++) {
             if (!s[k].nseg) continue;
@@ -49,7 +49,7 @@ uint32_t lvlip_snd_plan(lvlip_snd_flow *s, uint32_t nflows, uint32_t *nfd)
         }
         const int ok = ranges_disjoint(r, m);
         free(r);
-        if (!ok) return NONE;
+        if (!ok) return FLOW_NONE;
     }
     uint32_t slot = 0;
     for (uint32_t k = 0; k < nflows; k++) {
@@ -79,17 +79,16 @@ int lvlip_snd_cpu(const lvlip_lro_flow *f, const lvlip_snd_flow *s, uint32_t nfl
     for (uint32_t i = 0; i < n; i++) {
         const lvlip_lro_rec *r = &rec[i];
         const uint32_t k = rec_ack_flow(r, f, nflows);
-        if (k == NONE) continue;
+        if (k == FLOW_NONE) continue;
         const uint32_t d = r->ack_seq - s[k].snd_una, span = s[k].snd_nxt - s[k].snd_una;
-        if (d == 0) {
-            res[k].n_dup++;
-        } else if (d <= span) { /* src/tcp_input.c:330-331: snd_una only ever rises */
+        switch (flow_ack_class(d, span)) {
+        case FLOW_ACK_NEW:
             res[k].n_new++;
             if (d > res[k].acked) res[k].acked = d;
-        } else if (d >= 0x80000000u) { /* :338 */
-            res[k].n_old++;
-        } else { /* :343 */
-            res[k].n_beyond++;
+            break;
+        case FLOW_ACK_DUP: res[k].n_dup++; break;
+        case FLOW_ACK_OLD: res[k].n_old++; break;
+        default: res[k].n_beyond++;
         }
     }
     for (uint32_t k = 0; k < nflows; k++) {
@@ -109,12 +108,12 @@ int lvlip_snd_cpu(const lvlip_lro_flow *f, const lvlip_snd_flow *s, uint32_t nfl
 
 /* ------------------------------------------------------------ retransmit -- */
 
-/* one slot: queue entry e of flow k (NONE: dead) rewritten in place as tcp_transmit_skb leaves it */
+/* one slot: queue entry e of flow k (FLOW_NONE: dead) rewritten in place as tcp_transmit_skb leaves it */
 static void rtx_slot(const lvlip_lro_flow *f, const lvlip_lro_result *lro, const lvlip_snd_flow *s, uint32_t k,
                      uint32_t e, void *base, const lvlip_frame_desc *fd, lvlip_frame_desc *o)
 {
     o->offset = 0, o->len = 0, o->reserved = 0;
-    if (e == NONE) return;
+    if (e == FLOW_NONE) return;
     const lvlip_frame_desc d = fd[e];
     uint8_t *p = (uint8_t *)base + d.offset, *ih = p + 14, *th = p + 34;
     uint32_t iplen, hl;
@@ -146,7 +145,7 @@ int lvlip_rtx_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, const lv
         const uint32_t popped = snd ? snd[k].popped : 0u;
         for (uint32_t j = 0; j < s[k].rtx; j++) {
             const int live = popped < s[k].nseg && j < s[k].nseg - popped;
-            rtx_slot(f, lro, s, k, live ? s[k].seg0 + popped + j : NONE, base, fd, &fd_out[s[k].slot0 + j]);
+            rtx_slot(f, lro, s, k, live ? s[k].seg0 + popped + j : FLOW_NONE, base, fd, &fd_out[s[k].slot0 + j]);
         }
     }
     return LVLIP_OK;
@@ -165,7 +164,7 @@ int lvlip_rtx_sack_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, con
         uint32_t q = popped < s[k].nseg ? popped : s[k].nseg;
         for (uint32_t j = 0; j < s[k].rtx; j++) {
             while (q < s[k].nseg && sacked && sacked[s[k].seg0 + q] != 0) q++;
-            const uint32_t e = q < s[k].nseg ? s[k].seg0 + q++ : NONE;
+            const uint32_t e = q < s[k].nseg ? s[k].seg0 + q++ : FLOW_NONE;
             pick[s[k].slot0 + j] = e;
             rtx_slot(f, lro, s, k, e, base, fd, &fd_out[s[k].slot0 + j]);
         }

@@ -78,13 +78,13 @@
 #include <stdint.h>
 
 #include "csum_dev.h"
+#include "flow_step.h"
 #include "row_copy.h"
 #include "tcp_hdr_dev.h"
 #include "wave_ops.h"
 
 namespace lvlip {
 
-constexpr uint32_t SND_NONE = 0xFFFFFFFFu;
 constexpr int SND_PEEL = 4;                      // flows a wave reduces before lanes go alone
 constexpr uint32_t SND_WAVES = 4;                // flows per workgroup of k_snd_fin
 constexpr uint32_t RTX_ROW = 16;                 // lanes per slot
@@ -98,22 +98,22 @@ __global__ __launch_bounds__(256) void k_snd_rec(const lvlip_lro_flow* f, const 
                                                  const lvlip_lro_rec* rec, uint32_t n, lvlip_snd_result* res) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    uint32_t flow = SND_NONE, cls = 4u, d = 0u;  // cls: 0 new, 1 duplicate, 2 old, 3 beyond, 4 no ACK
+    uint32_t flow = FLOW_NONE, cls = 4u, d = 0u;  // cls: flow_ack_class (flow_step.h), or 4: no ACK
     if (i < n) {
         const uint4 r = load_global(reinterpret_cast<uint64_t>(rec + i));  // flow, rel, dlen | status | flags, ack_seq
         flow = rec_ack_flow(r, f, nflows);
-        if (flow != SND_NONE) {
+        if (flow != FLOW_NONE) {
             const uint32_t una = s[flow].snd_una, span = s[flow].snd_nxt - una;
             d = r.w - una;
-            cls = d == 0u ? 1u : d <= span ? 0u : d >= 0x80000000u ? 2u : 3u;  // :330, :338, :343
+            cls = flow_ack_class(d, span);
         }
     }
     const bool pending = wave_peel<SND_PEEL>(cls < 4u, flow, [=](uint32_t fl, bool mine) {
-        const uint32_t c0 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == 0u));
-        const uint32_t c1 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == 1u));
-        const uint32_t c2 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == 2u));
-        const uint32_t c3 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == 3u));
-        const uint32_t mx = wave_max_u32(mine && cls == 0u ? d : 0u);
+        const uint32_t c0 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == FLOW_ACK_NEW));
+        const uint32_t c1 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == FLOW_ACK_DUP));
+        const uint32_t c2 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == FLOW_ACK_OLD));
+        const uint32_t c3 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mine && cls == FLOW_ACK_BEYOND));
+        const uint32_t mx = wave_max_u32(mine && cls == FLOW_ACK_NEW ? d : 0u);
         uint32_t* w = reinterpret_cast<uint32_t*>(res + fl);  // snd_una acked n_new n_dup n_old n_beyond popped inflight
         const uint32_t cnt = lane == 0u ? c0 : lane == 1u ? c1 : lane == 2u ? c2 : c3;
         if (lane < 4u && cnt) atomicAdd(w + 2u + lane, cnt);
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_snd_rec(const lvlip_lro_flow* f, const 
     if (pending) {
         uint32_t* w = reinterpret_cast<uint32_t*>(res + flow);
         atomicAdd(w + 2u + cls, 1u);
-        if (cls == 0u) atomicMax(w + 1, d);
+        if (cls == FLOW_ACK_NEW) atomicMax(w + 1, d);
     }
 }
 
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void k_pick(const lvlip_snd_flow* s, const lvl
         if (open && rank < rtx) out[rank] = seg0 + (uint32_t)i;
         found += (uint32_t)__builtin_popcountll(b);
     }
-    for (uint64_t j = (uint64_t)found + lane; j < rtx; j += 64u) out[j] = SND_NONE;
+    for (uint64_t j = (uint64_t)found + lane; j < rtx; j += 64u) out[j] = FLOW_NONE;
 }
 
 // with pick, the slot's queue entry is pick[slot] (0xFFFFFFFF: dead), as k_pick left it, not popped + j
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void k_rtx(const lvlip_lro_flow* f, const lvli
     // flows that share a slot0 only the last has a slot)
     const uint32_t slo = slot_owner<&lvlip_snd_flow::slot0>(s, nflows, g);
     const lvlip_snd_flow* t = s + slo;
-    uint32_t e = SND_NONE;  // the slot's queue entry
+    uint32_t e = FLOW_NONE;  // the slot's queue entry
     if (pick) {
         if (inside) e = pick[g];
     } else {
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void k_rtx(const lvlip_lro_flow* f, const lvli
         const uint32_t popped = snd ? snd[slo].popped : 0u;
         if (inside && j < t->rtx && popped < nseg && j < nseg - popped) e = t->seg0 + popped + j;
     }
-    bool live = e != SND_NONE;
+    bool live = e != FLOW_NONE;
 
     uint4 d = make_uint4(0u, 0u, 0u, 0u);  // the queue entry: offset lo, hi, len, reserved
     if (live) d = load_global(reinterpret_cast<uint64_t>(fd + e));
@@ -291,8 +291,7 @@ static int rtx_launch(const lvlip_lro_flow* f, const lvlip_lro_result* lro, cons
     if (nslots == 0) return LVLIP_OK;
     if (!f || !s || !base || !fd || !fd_out) return LVLIP_EINVAL;
     if (nflows == 0 || nflows > LVLIP_LRO_MAX_FLOWS || nslots > LVLIP_MAX_BATCH) return LVLIP_EINVAL;
-    if (((uintptr_t)f & 7u) || ((uintptr_t)s & 7u) || ((uintptr_t)lro & 15u) || ((uintptr_t)snd & 15u) ||
-        ((uintptr_t)fd & 15u) || ((uintptr_t)fd_out & 15u) || ((uintptr_t)pick & 3u))
+    if (any_misaligned<8>(f, s) || any_misaligned<16>(lro, snd, fd, fd_out) || any_misaligned<4>(pick))
         return LVLIP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (pick) {
@@ -314,9 +313,7 @@ int lvlip_snd_dev(const lvlip_lro_flow* f, const lvlip_snd_flow* s, uint32_t nfl
     if (nflows == 0 || n == 0) return LVLIP_OK;
     if (!f || !s || !rec || !base || !fd || !res) return LVLIP_EINVAL;
     if (n > LVLIP_MAX_BATCH || nflows > LVLIP_LRO_MAX_FLOWS) return LVLIP_EINVAL;
-    if (((uintptr_t)f & 7u) || ((uintptr_t)s & 7u) || ((uintptr_t)rec & 15u) || ((uintptr_t)fd & 15u) ||
-        ((uintptr_t)res & 15u))
-        return LVLIP_EINVAL;
+    if (any_misaligned<8>(f, s) || any_misaligned<16>(rec, fd, res)) return LVLIP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     int rc = lvlip_launch_status(hipMemsetAsync(res, 0, (size_t)nflows * sizeof *res, st), "lvlip_snd_dev: memset");
     if (rc != LVLIP_OK) return rc;

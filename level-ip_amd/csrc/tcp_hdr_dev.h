@@ -130,3 +130,11 @@ extern "C" int lvlip_launch_status(hipError_t e, const char* what);
 
 // the same for the kernel just launched
 static inline int lvlip_launched(const char* what) { return lvlip_launch_status(hipGetLastError(), what); }
+
+// An entry point's alignment refusal: whether one of the pointers is not a
+// multiple of A bytes (8 for flow arrays, 16 for records, descriptors and
+// results, which the kernels load as vectors).  NULL passes.
+template <uintptr_t A, class... P>
+static inline bool any_misaligned(const P*... p) {
+    return (... || (((uintptr_t)p & (A - 1u)) != 0u));
+}

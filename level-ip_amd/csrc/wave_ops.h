@@ -1,8 +1,9 @@
 // wave_ops.h — what one 64-lane wave does as a whole in the protocol kernels:
 // the 64-way search over a sorted key array that k_adv_emit (adv_kernels.hip)
 // and k_sack_mark (sack_kernels.hip) find a flow's range with, the sums, maxima
-// and scans they and k_snd_rec (snd_kernels.hip) reduce with, and the
-// flow-by-flow loop k_snd_rec and k_sack_parse run before their atomics.
+// and scans they, k_snd_rec (snd_kernels.hip), k_wnd_rec (rto_kernels.hip) and
+// k_cc_sum (cc_kernels.hip) reduce with, and the flow-by-flow loop k_snd_rec,
+// k_wnd_rec and k_sack_parse run before their atomics.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,6 +23,23 @@ __device__ __forceinline__ uint32_t wave_add_u32(uint32_t v) {
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
+    return v;
+}
+
+// the same on 64-bit values: k_cc_sum's byte sum (cc_kernels.hip) and k_wnd_rec's keys (rto_kernels.hip)
+__device__ __forceinline__ uint64_t wave_add_u64(uint64_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, off, 64);
+    return v;
+}
+
+// and their maximum
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t o = __shfl_xor(v, off, 64);
+        v = v > o ? v : o;
+    }
     return v;
 }
 
