@@ -1208,9 +1208,10 @@ int lvlip_push_dev(const lvlip_lro_flow *f, const lvlip_lro_result *lro, lvlip_s
  * it.  With LVLIP_WND_APPLY and a non-NULL w, w[k].wnd = min(t[k].snd_wnd,
  * t[k].wnd_cap) for EVERY flow; nothing else of w and t is written.  wnd_cap is
  * where a congestion window plugs in.  n == 0 is not a no-op: no flow has a
- * winner, res is written and the window applied.  Out of scope: the
- * zero-window persist timer (RFC 1122 4.2.2.17); a flow whose peer closes the
- * window waits for the next ACK that opens it. */
+ * winner, res is written and the window applied.  A flow whose peer closes the
+ * window waits for the next ACK that opens it; the zero-window persist timer
+ * (RFC 1122 4.2.2.17) that covers the loss of that ACK is lvlip_persist_*
+ * below. */
 #define LVLIP_RTO_FAST    0x1u        /* flags of lvlip_rto_*: step 4 */
 #define LVLIP_RTO_TIMEOUT 1u          /* lvlip_rto_result.fired */
 #define LVLIP_RTO_FASTRTX 2u
@@ -1372,7 +1373,8 @@ int lvlip_rto_dev(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lv
  * Departures.  The reference has no congestion control.  One step per batch,
  * not per ACK.  No retransmit of the next hole on a partial ACK:
  * lvlip_rtx_sack_* with rtx > 1 re-sends several holes when the flow fires, and
- * the timer covers the rest.  No ECN, no pacing, no persist timer. */
+ * the timer covers the rest.  No ECN, no pacing.  The persist timer is
+ * lvlip_persist_* below. */
 #define LVLIP_CC_MAX_WND 0x40000000u
 /* event bits of lvlip_cc_result.event */
 #define LVLIP_CC_EV_TIMEOUT   0x01u   /* step 1 cut cwnd to one mss */
@@ -1431,6 +1433,123 @@ int lvlip_cc_cpu(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lvl
 int lvlip_cc_dev(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lvlip_rto_result *prev,
                  lvlip_cc_flow *c, lvlip_rto_flow *t, uint32_t nflows, const lvlip_frame_desc *fd,
                  const uint8_t *sacked, lvlip_cc_result *res, void *stream);
+
+/* ---- f2 on the device: the persist timer -------------------------------------
+ *
+ * When the peer advertises a window below one segment lvlip_push_* appends
+ * nothing; once the queue has drained lvlip_rto_* stops its timer (steps 1 and
+ * 3), and from then on nothing on the sender produces a frame.  If the one ACK
+ * that reopens the window is lost the connection hangs for good.  RFC 1122
+ * 4.2.2.17 makes the zero-window probe a MUST for this reason; lvlip_persist_*
+ * is that timer and that probe.  The reference has no persist timer and never
+ * reads the window field: like lvlip_wnd_* and lvlip_cc_*, a departure that
+ * follows the RFCs.
+ *
+ * lvlip_persist_flow k is the persist state of flow k of the reverse plan, as
+ * lvlip_rto_flow k is its retransmission timer.  The struct has no padding.
+ * The caller starts a flow all zero.
+ *
+ * Where it sits in the loop.  Once per round, after lvlip_push_* and
+ * lvlip_rto_* and before the retransmit, with the `now` lvlip_rto_* got; s and
+ * w are as the push left them; out and fd_out go to the wire beside the
+ * push's and the retransmit's frames.
+ *
+ * One call, for flow k, from the values at entry, in this fixed order:
+ *   0 dead     t[k].dead set: p[k] and t[k] do not change, res[k] is all zero,
+ *              fd_out[k] = {64 k, 0, 0} and no byte of out is written.
+ *   1 stalled  s.nseg == 0 and w.unsent > 0 and w.wnd < min(w.unsent, w.mss):
+ *              nothing is in flight (so the retransmission timer is stopped
+ *              and no ACK is owed), there are bytes to send, and the window,
+ *              not cap or push, keeps the first segment back.  A window of
+ *              1 .. mss - 1 against a full segment counts: lvlip_push_* sends
+ *              whole segments only.
+ *   2 not stalled.  If p.armed: p[k] becomes all zero and t[k].dupacks = 0.
+ *              The answers to probes raise n_dup in lvlip_snd_* and so dupacks
+ *              in lvlip_rto_* step 1; they are not duplicate ACKs in RFC
+ *              5681's sense, because no data was outstanding, and left in
+ *              place they would keep step 4 there ("below 3 at entry") from
+ *              ever firing for the first loss after the window reopens.
+ *              Nothing else of t is ever written.  No probe; res[k] is zero.
+ *   3 stalled and not armed.  armed = 1, probes = 0, interval = max(1,
+ *              min(t.rto, 60000)), expires = now + interval.  No probe;
+ *              res[k] = {0, interval, 0, 0}.
+ *   4 stalled and armed.  The timer's test is expires < now: strict and
+ *              unsigned, the test of lvlip_rto_* step 3 (src/timer.c:71).  If
+ *              it holds the flow FIRES: probes += 1 (it stops at 2^32 - 1),
+ *              interval = min(2 * interval, 60000) formed in 64 bits, expires =
+ *              now + interval, res[k] = {1, interval, probes, snd_una - 1}.
+ *              Otherwise res[k] = {0, interval, probes, 0}.  There is no
+ *              cut-off: RFC 1122 requires probing for as long as the peer
+ *              answers; giving up is lvlip_rto_*'s `dead` and the host's.
+ * Arming and firing never happen in one call.
+ *
+ * The probe of a fired flow is the Linux form: zero length, seq one below
+ * snd_una.  It takes no sequence space and touches no queue entry, no fd
+ * region and no scoreboard byte.  It is the 54 bytes at out + 64 k; bytes
+ * 54 .. 63 of the slot keep their contents.  Ethernet and IPv4 are w[k].hdr's
+ * with total length htons(40), the id as given and the header checksum
+ * checksum(ih, 20, 0), stored raw.  TCP is w[k].hdr's with seq = htonl(s.snd_una
+ * - 1), ack_seq = htonl(f[k].rcv_nxt + lro[k].delivered) (lro may be NULL: 0),
+ * window = htons(s[k].win) (the fields lvlip_push_* and lvlip_rtx_* patch),
+ * byte 13 the template's with PSH and FIN cleared (what a segment that is not
+ * the last gets, src/tcp_output.c:466) and csum = checksum(tcp, 20, saddr +
+ * daddr + htons(6) + htons(20)) with the wrapping u32 seed of every other
+ * frame writer here.  fd_out[k] = {64 k, 54, 0}; a flow that did not fire gets
+ * {64 k, 0, 0} and no byte of out.
+ *
+ * Out of scope.  The receiver's side of a probe stays as it is: lvlip_lro_*
+ * reports it as NO_DATA with rel == 0xFFFFFFFF, lvlip_ack_* answers it only
+ * under LVLIP_ACK_ALL; RFC 793 says an unacceptable segment elicits an ACK, and
+ * arranging that is the receiving caller's step.  Also out of scope: the
+ * one-byte BSD probe, sender-side SWS override timers, advertising rcv_wnd
+ * from the device, FIN. */
+#define LVLIP_PERSIST_MAX_MS 60000u
+#define LVLIP_PERSIST_SLOT   64u      /* probe k is the 54 bytes at out + 64 k */
+
+typedef struct lvlip_persist_flow {   /* one per planned reverse flow; sizeof == 16, no padding */
+    uint32_t expires;                 /* meaningful while armed */
+    uint32_t interval;                /* ms, 1 .. 60000 while armed, else 0 */
+    uint32_t probes;                  /* probes sent since the timer was armed; saturates */
+    uint8_t  armed;                   /* 0 or 1 */
+    uint8_t  reserved[3];             /* 0 */
+} lvlip_persist_flow;
+
+typedef struct lvlip_persist_result { /* one per planned flow; sizeof == 16 */
+    uint32_t fired, interval, probes, seq;   /* seq: the probe's sequence number, host order; 0 if none */
+} lvlip_persist_result;
+
+/* Host only: 0 when every p[k] is a state these calls take, LVLIP_EINVAL for
+ * armed other than 0 and 1, nonzero reserved bytes, interval above 60000 or
+ * interval 0 while armed, a NULL p with nflows > 0 or nflows above
+ * LVLIP_LRO_MAX_FLOWS.  The _dev form cannot look: the state is in HBM; the
+ * caller checks it here before it uploads it.  Nothing is written. */
+int lvlip_persist_check(const lvlip_persist_flow *p, uint32_t nflows);
+
+/* On the calling thread, the frame through the writer lvlip_push_cpu uses.  f,
+ * lro (may be NULL), s and w are read; t[k].dupacks, p, out (64 bytes per
+ * flow, any alignment), fd_out and res are written as above.  Returns 0, or
+ * LVLIP_EINVAL with nothing written: NULL f, s, w, t, p, out, fd_out or res
+ * with nflows > 0, nflows above LVLIP_LRO_MAX_FLOWS, or a p
+ * lvlip_persist_check refuses.  nflows == 0 is a no-op.  Reentrant. */
+int lvlip_persist_cpu(const lvlip_lro_flow *f, const lvlip_lro_result *lro, const lvlip_snd_flow *s,
+                      const lvlip_push_flow *w, lvlip_rto_flow *t, lvlip_persist_flow *p, uint32_t nflows,
+                      uint32_t now, void *out, lvlip_frame_desc *fd_out, lvlip_persist_result *res);
+
+/* The same bytes in ONE launch on the caller's stream (asynchronous; no
+ * allocation, copy, atomics, LDS, workspace or synchronisation): eight lanes
+ * per flow all load the flow's words, build the 54 bytes in registers and each
+ * keep one aligned 16-byte chunk of the frame, so that no byte outside it is
+ * stored; the first lane stores p[k], res[k], fd_out[k] and, only when step 2
+ * asks for it, the four bytes of t[k].dupacks.  All pointers are device
+ * pointers: f, s, w, t and p 8-B aligned, lro, fd_out and res 16-B aligned, out
+ * any alignment.  The NULL and limit refusals of lvlip_persist_cpu and a
+ * misaligned pointer are LVLIP_EINVAL before any HIP call (p and w are not
+ * looked at: the caller checked and planned them); LVLIP_ENODEV without a
+ * device; a failed launch is LVLIP_EHIP (lvlip_last_hip_error).  Measured:
+ * DESIGN.md section 9m. */
+int lvlip_persist_dev(const lvlip_lro_flow *f, const lvlip_lro_result *lro, const lvlip_snd_flow *s,
+                      const lvlip_push_flow *w, lvlip_rto_flow *t, lvlip_persist_flow *p, uint32_t nflows,
+                      uint32_t now, void *out, lvlip_frame_desc *fd_out, lvlip_persist_result *res, void *stream);
 
 /* RFC 1071 pseudo-header seed with the carries folded back (for RX verify of
  * checksums produced by RFC-correct peers). */

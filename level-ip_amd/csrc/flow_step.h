@@ -1,9 +1,10 @@
 /*
  * flow_step.h — one flow's step of the protocol state machines, once for both
  * sides: the retransmission timer, the congestion window, the peer's window,
- * the push count and the class of an ACK.  The CPU forms (rto_cpu.c, cc_cpu.c,
- * push_cpu.c, snd_cpu.c) call these on the flow in the caller's array, the
- * kernels (rto_, cc_, push_ and snd_kernels.hip) on a flow in registers.
+ * the push count, the class of an ACK and the persist timer.  The CPU forms
+ * (rto_cpu.c, cc_cpu.c, push_cpu.c, snd_cpu.c, persist_cpu.c) call these on the
+ * flow in the caller's array, the kernels (rto_, cc_, push_, snd_ and
+ * persist_kernels.hip) on a flow in registers.
  * Every function takes scalars and one flow; none sees a batch.  How a flow's
  * words travel between HBM and registers, which lane runs the step and what is
  * reduced around it stays in the kernels.  Plain C99, not installed.
@@ -188,6 +189,47 @@ FLOW_FN uint32_t flow_push_count(const lvlip_push_flow *w, const lvlip_snd_flow 
     const uint64_t b = (uint64_t)m * mss;
     *bytes = b < unsent ? (uint32_t)b : unsent;
     return m;
+}
+
+typedef struct flow_persist_out {
+    uint32_t fired;    /* 0 or 1: a probe goes out */
+    uint32_t interval; /* lvlip_persist_result's interval and probes */
+    uint32_t probes;
+    uint32_t clear; /* 0 or 1: the timer's dupacks are to be zeroed */
+} flow_persist_out;
+
+/* Steps 0-4 of lvlip_persist_* on *x, for a flow whose queue holds nseg
+ * entries, whose write side has `unsent` bytes ready, a window of wnd and
+ * segments of mss, and whose retransmission timer stands at rto (and is dead
+ * or not), at time now.  A dead flow is left as it is. */
+FLOW_FN flow_persist_out flow_persist_step(lvlip_persist_flow *x, uint32_t dead, uint32_t nseg, uint32_t unsent,
+                                           uint32_t wnd, uint32_t mss, uint32_t rto, uint32_t now)
+{
+    flow_persist_out o = {0u, 0u, 0u, 0u};
+    if (dead) return o;
+    const uint32_t first = unsent < mss ? unsent : mss; /* the segment lvlip_push_* would send next */
+    if (!(nseg == 0u && unsent > 0u && wnd < first)) {  /* 2: not stalled */
+        if (x->armed) {
+            x->expires = 0u, x->interval = 0u, x->probes = 0u;
+            x->armed = 0, x->reserved[0] = 0, x->reserved[1] = 0, x->reserved[2] = 0;
+            o.clear = 1u; /* the answers to probes are no duplicate ACKs of RFC 5681 */
+        }
+        return o;
+    }
+    if (!x->armed) { /* 3: the timer starts; the first probe waits one interval */
+        const uint32_t iv = rto < LVLIP_PERSIST_MAX_MS ? rto : LVLIP_PERSIST_MAX_MS;
+        x->armed = 1, x->probes = 0u;
+        x->interval = iv ? iv : 1u;
+        x->expires = now + x->interval;
+    } else if (x->expires < now) { /* 4: src/timer.c:71, as flow_rto_step */
+        const uint64_t twice = 2ull * x->interval;
+        o.fired = 1u;
+        if (x->probes != 0xFFFFFFFFu) x->probes++;
+        x->interval = twice < LVLIP_PERSIST_MAX_MS ? (uint32_t)twice : LVLIP_PERSIST_MAX_MS;
+        x->expires = now + x->interval;
+    }
+    o.interval = x->interval, o.probes = x->probes;
+    return o;
 }
 
 #endif

@@ -268,6 +268,10 @@ SIGNATURES = {
     "lvlip_cc_check": (_INT, [_P, _U32]),
     "lvlip_cc_cpu": (_INT, [_P, _P, _P, _P, _P, _U32, _P, _P, _P]),
     "lvlip_cc_dev": (_INT, [_P, _P, _P, _P, _P, _U32, _P, _P, _P, _P]),
+    # f2 on the device: the persist timer (persist_cpu.c, persist_kernels.hip)
+    "lvlip_persist_check": (_INT, [_P, _U32]),
+    "lvlip_persist_cpu": (_INT, [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P]),
+    "lvlip_persist_dev": (_INT, [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P]),
     "lvlip_auto_kernel": (_INT, [_I32, _U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (_U32, [_U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (_STR, []),
@@ -1520,6 +1524,79 @@ def cc_dev(snd_t, snd_res_t, prev_t, cc_t, rto_t, fd_t=None, sacked_t=None, res_
     _check(_lib.lvlip_cc_dev(snd_t.data_ptr(), _tptr(snd_res_t), _tptr(prev_t), cc_t.data_ptr(), rto_t.data_ptr(),
                              nflows, _tptr(fd_t), _tptr(sacked_t), res_t.data_ptr(), s.cuda_stream), "lvlip_cc_dev")
     return res_t[:CC_RESULT_DTYPE.itemsize * nflows]
+
+
+# ---------------------------------------- f2 on the device: the persist timer --
+
+# struct lvlip_persist_flow / lvlip_persist_result (16 B each), include/lvlip_skb.h
+PERSIST_FLOW_DTYPE = np.dtype([("expires", "<u4"), ("interval", "<u4"), ("probes", "<u4"), ("armed", "u1"),
+                               ("reserved", "u1", (3,))])
+PERSIST_RESULT_DTYPE = np.dtype([("fired", "<u4"), ("interval", "<u4"), ("probes", "<u4"), ("seq", "<u4")])
+PERSIST_MAX_MS, PERSIST_SLOT = 60000, 64
+assert PERSIST_FLOW_DTYPE.itemsize == 16 and PERSIST_RESULT_DTYPE.itemsize == 16
+
+
+def persist_flows(nflows: int) -> np.ndarray:
+    """nflows fresh lvlip_persist_flow states: no timer."""
+    return np.zeros(nflows, dtype=PERSIST_FLOW_DTYPE)
+
+
+def persist_check(persist: np.ndarray) -> None:
+    """lvlip_persist_check: ValueError for a state the calls refuse."""
+    _planned(persist, PERSIST_FLOW_DTYPE, "persist: a contiguous PERSIST_FLOW_DTYPE array", writeable=False)
+    if _lib.lvlip_persist_check(_aptr(persist), persist.size) != OK:
+        raise ValueError("refused persist state (armed, reserved, interval, too many)")
+
+
+def persist_cpu(flows: np.ndarray, lro_res, snd: np.ndarray, push: np.ndarray, rto: np.ndarray, persist: np.ndarray,
+                now: int, out: Optional[np.ndarray] = None):
+    """lvlip_persist_cpu: one round of the zero-window persist timer, IN PLACE
+    in persist and in rto["dupacks"].  flows, snd and push as push_* left them;
+    lro_res (LRO_RESULT_DTYPE) may be None.  Returns (out, fd_out, res): the
+    probes' buffer (PERSIST_SLOT bytes per flow; the caller's `out`, or a new
+    zeroed one), FRAME_DESC_DTYPE and PERSIST_RESULT_DTYPE per flow."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    snd = np.ascontiguousarray(snd, dtype=SND_FLOW_DTYPE)
+    push = np.ascontiguousarray(push, dtype=PUSH_FLOW_DTYPE)
+    _planned(rto, RTO_FLOW_DTYPE, "rto: a writeable contiguous RTO_FLOW_DTYPE array")
+    _planned(persist, PERSIST_FLOW_DTYPE, "persist: a writeable contiguous PERSIST_FLOW_DTYPE array")
+    if lro_res is not None:
+        lro_res = np.ascontiguousarray(lro_res, dtype=LRO_RESULT_DTYPE)
+    n = flows.size
+    if any(a.size != n for a in (snd, push, rto, persist)) or (lro_res is not None and lro_res.size != n):
+        raise ValueError("one send side, write side, timer state and persist state per flow")
+    out = _out_u8(out, PERSIST_SLOT * n)
+    if not out.flags.writeable:
+        raise ValueError("out: writeable")
+    fd_out = np.zeros(n, dtype=FRAME_DESC_DTYPE)
+    res = np.zeros(n, dtype=PERSIST_RESULT_DTYPE)
+    _check(_lib.lvlip_persist_cpu(_aptr(flows), _aptr(lro_res), _aptr(snd), _aptr(push), _aptr(rto), _aptr(persist),
+                                  n, now & 0xFFFFFFFF, _aptr(out), _aptr(fd_out), _aptr(res)), "lvlip_persist_cpu")
+    return out, fd_out, res
+
+
+def persist_dev(flows_t, lro_res_t, snd_t, push_t, rto_t, persist_t, now: int, out_t, fd_out_t=None, res_t=None,
+                stream=None):
+    """lvlip_persist_dev on CUDA uint8 tensors: flows_t 48, snd_t 32, push_t
+    112, rto_t 32 and persist_t 16 bytes per flow (persist_t and rto_t's
+    dupacks updated in place), lro_res_t (48 per flow) may be None; out_t
+    PERSIST_SLOT bytes per flow at any alignment.  Returns (fd_out_t, res_t):
+    16 bytes per flow each (new tensors unless given).  One launch on `stream`
+    (default: current), asynchronous."""
+    nflows = _nbytes(flows_t) // LRO_FLOW_DTYPE.itemsize
+    _need(snd_t, "snd_t", SND_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(push_t, "push_t", PUSH_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(rto_t, "rto_t", RTO_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(persist_t, "persist_t", PERSIST_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(lro_res_t, "lro_res_t", LRO_RESULT_DTYPE.itemsize, nflows, "flow", optional=True)
+    _need(out_t, "out_t", PERSIST_SLOT, nflows, "flow")
+    fd_out_t = _result(fd_out_t, "fd_out_t", 16, nflows, "flow", flows_t.device)
+    res_t = _result(res_t, "res_t", PERSIST_RESULT_DTYPE.itemsize, nflows, "flow", flows_t.device)
+    s = _stream(stream, flows_t.device)
+    _check(_lib.lvlip_persist_dev(flows_t.data_ptr(), _tptr(lro_res_t), snd_t.data_ptr(), push_t.data_ptr(),
+                                  rto_t.data_ptr(), persist_t.data_ptr(), nflows, now & 0xFFFFFFFF, out_t.data_ptr(),
+                                  fd_out_t.data_ptr(), res_t.data_ptr(), s.cuda_stream), "lvlip_persist_dev")
+    return fd_out_t[:16 * nflows], res_t[:PERSIST_RESULT_DTYPE.itemsize * nflows]
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
