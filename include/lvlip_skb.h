@@ -1551,6 +1551,126 @@ int lvlip_persist_dev(const lvlip_lro_flow *f, const lvlip_lro_result *lro, cons
                       const lvlip_push_flow *w, lvlip_rto_flow *t, lvlip_persist_flow *p, uint32_t nflows,
                       uint32_t now, void *out, lvlip_frame_desc *fd_out, lvlip_persist_result *res, void *stream);
 
+/* ---- f1: the receive buffer --------------------------------------------------- */
+
+/* The receiver's half of the loop, closed.  lvlip_lro_next_* only ever shrinks
+ * a flow's region of `out` from its front, and the window lvlip_ack_*
+ * advertises is whatever the host wrote into the template; a connection that
+ * outlives its region needed a host step.  lvlip_rbuf_* is what the reference's
+ * tcp_data_dequeue (src/tcp_data.c:49-85, the recv() side of tcp_data_queue)
+ * and the window field of tcp_transmit_skb (src/tcp_output.c:109) do, once per
+ * round: the application reads from the front of the
+ * flow's buffer, the buffer is used again once what was read outweighs what is
+ * left, the window that follows is advertised with RFC 1122 4.2.3.3's
+ * receiver-side silly-window avoidance, and a flow whose window opened with no
+ * data to acknowledge is marked as owing a window update.  So far these calls
+ * have a CPU form only: the state and the plan's piece0 are laid out for a
+ * device form that is not in the library yet.
+ *
+ * lvlip_rbuf_flow k is the buffer of flow k of the forward plan.  The buffer is
+ * the cap bytes at out + base_off; f[k]'s region [out_off, out_off + rcv_wnd) is
+ * its tail, the used = out_off - base_off bytes in front of it are stream bytes
+ * delivered in order, and the first `head` of those the application has read.
+ * Invariants against f[k], which lvlip_rbuf_plan and lvlip_rbuf_check test:
+ *   base_off <= f.out_off,  f.out_off + f.rcv_wnd == base_off + cap,
+ *   head <= f.out_off - base_off,  1 <= cap <= 2^30,  mss >= 1,  wscale <= 14,
+ *   reserved all zero, and the buffers [base_off, base_off + cap) pairwise
+ *   disjoint.
+ * A fresh flow has base_off = out_off, cap = rcv_wnd, head = 0 and adv_edge =
+ * rcv_nxt + rcv_wnd.  The struct has no padding.
+ *
+ * Where it sits in the loop.  lvlip_lro_* -> lvlip_lro_advance_carry* ->
+ * lvlip_lro_next_* -> lvlip_rbuf_* -> lvlip_ack_*.  The ACK after `next` builds
+ * the frame it would have built before it (above); it is given `gate` as its
+ * res and the t this call patched.
+ *
+ * One call, for flow k, from the values at entry, in this fixed order, with
+ * used = out_off - base_off and unread = used - head:
+ *   1 read     r = min(nread[k], unread) (nread NULL: 0).  With a sink the r
+ *              bytes at out + base_off + head are copied to sink + sink_off and
+ *              sink_off += r: tcp_data_dequeue's copy.  head += r.
+ *   2 live     span = the largest r_j over the blocks j < min(res[k].nsack, 4)
+ *              that count under lvlip_lro_advance_carry's rule against f[k] as
+ *              it stands (l < r_j <= rcv_wnd; "Carried blocks" above), 0 if
+ *              none does.  live = (used - head) + span: the unread bytes and
+ *              everything up to the end of the last island.
+ *   3 reuse    if head > 0 and live <= head: the live bytes at base_off + head
+ *              move to base_off (the two ranges cannot overlap), out_off -=
+ *              head, rcv_wnd += head, head = 0.  What is copied is at most
+ *              what was read since the last move, so reuse costs at most one
+ *              more copy per stream byte; with live == 0 it is a rewind and
+ *              copies nothing.  Islands keep their sequence numbers: res[k]'s
+ *              sack[] stays valid as the next carry.
+ *   4 window   edge = rcv_nxt + rcv_wnd, grow = (edge - adv_edge) mod 2^32.  If
+ *              grow >= min(ceil(cap / 2), mss) then adv_edge = edge (RFC 1122
+ *              4.2.3.3 with Fr = 1/2); otherwise the edge stays (RFC 793: never
+ *              shrink).  a = (adv_edge - rcv_nxt) mod 2^32 are the advertised
+ *              bytes; min(a >> wscale, 65535) is stored htons into bytes 48-49
+ *              of t[k].hdr.  No other byte of t is written.
+ *   5 update   gate[k] = all 48 bytes of res[k]; when step 4 moved the edge and
+ *              res[k].placed == 0, gate[k].placed = 1, so that lvlip_ack_*
+ *              without LVLIP_ACK_ALL sends the window update.  res is only read.
+ * rres[k] = {r, unread and head as the call leaves them, the bytes step 3
+ * moved, a, the field, LVLIP_RBUF_* bits, 0}.
+ * Only f[k].out_off, f[k].rcv_wnd, p[k], t[k].hdr[48..49], gate, rres, the moved
+ * bytes inside the flow's own buffer and sink are written.
+ *
+ * Departures from the reference.  tcp_data_dequeue frees the skbs it has
+ * copied out; here the bytes that are left move to the buffer's front.  The
+ * reference advertises a constant window (src/tcp_output.c:109, tcb.rcv_wnd is
+ * set once) and so never shrinks or reopens one.  lvlip_snd_flow.win, the window
+ * on this host's own data frames, is not written: it lives in the reverse
+ * plan's index space, and copying rres[k].field there is the caller's.  The ACK
+ * RFC 793 owes an unacceptable segment (a probe among them) stays the caller's
+ * step, as in the persist section. */
+#define LVLIP_RBUF_PIECE    16384u    /* bytes of a flow's range that make one copy piece (piece0) */
+#define LVLIP_RBUF_MOVED    0x1u      /* lvlip_rbuf_result.flags: step 3 reused the buffer */
+#define LVLIP_RBUF_ADVANCED 0x2u      /* step 4 moved the advertised edge */
+#define LVLIP_RBUF_UPDATE   0x4u      /* step 5 raised gate.placed: a window update is owed */
+
+typedef struct lvlip_rbuf_flow {      /* one per planned forward flow; sizeof == 48, no padding */
+    uint64_t base_off;                /* start of the flow's buffer, from the out base; any alignment */
+    uint64_t sink_off;                /* where the next byte read goes, from the sink base */
+    uint32_t cap;                     /* bytes of the buffer, 1 .. 2^30 */
+    uint32_t head;                    /* offset from base_off of the first unread byte */
+    uint32_t adv_edge;                /* host order: the right edge last advertised */
+    uint32_t piece0;                  /* written by lvlip_rbuf_plan: the first of the flow's copy pieces */
+    uint16_t mss;                     /* >= 1: the peer's segment size, for step 4 */
+    uint8_t  wscale;                  /* 0 .. 14: the shift this host announced (RFC 7323) */
+    uint8_t  reserved[13];            /* 0 */
+} lvlip_rbuf_flow;
+
+typedef struct lvlip_rbuf_result {    /* one per planned flow; sizeof == 32 */
+    uint32_t read, unread, head, moved, adv, field, flags, reserved;
+} lvlip_rbuf_result;
+
+/* Host only: validates p against the planned flows f (the invariants above)
+ * and writes p[k].piece0 = the sum of ceil(p[j].cap / LVLIP_RBUF_PIECE) over
+ * j < k, the index space the copy kernel's workgroups stride over.  Returns
+ * nflows, or 0xFFFFFFFF for a broken invariant, a NULL p or f with nflows > 0,
+ * nflows above LVLIP_LRO_MAX_FLOWS, more than 2^31 pieces, or no memory for the
+ * overlap check, with nothing written.  *npieces (may be NULL) gets the sum
+ * over all flows. */
+uint32_t lvlip_rbuf_plan(lvlip_rbuf_flow *p, const lvlip_lro_flow *f, uint32_t nflows, uint64_t *npieces);
+
+/* Host only: 0 when p is a state these calls take against f (the invariants
+ * and the piece0 of lvlip_rbuf_plan), LVLIP_EINVAL otherwise and for a NULL p or
+ * f with nflows > 0 or nflows above LVLIP_LRO_MAX_FLOWS, LVLIP_ENOMEM if the
+ * overlap check's allocation fails.  Every call leaves a state the check
+ * takes.  Nothing is written. */
+int lvlip_rbuf_check(const lvlip_rbuf_flow *p, const lvlip_lro_flow *f, uint32_t nflows);
+
+/* On the calling thread, the copies with memcpy.  res and nread (may be NULL)
+ * are read; f, p, t, gate, rres, out and sink (may be NULL: what is read is
+ * dropped and sink_off stays) are written as above.  gate must not be res.
+ * Returns 0, or with nothing written LVLIP_EINVAL: NULL f, res, p, t, out, gate
+ * or rres with nflows > 0, gate == res, nflows above LVLIP_LRO_MAX_FLOWS, or a p
+ * lvlip_rbuf_check refuses (LVLIP_ENOMEM as there).  nflows == 0 is a no-op.
+ * Reentrant. */
+int lvlip_rbuf_cpu(lvlip_lro_flow *f, const lvlip_lro_result *res, lvlip_rbuf_flow *p, lvlip_ack_tmpl *t,
+                   uint32_t nflows, const uint32_t *nread, void *out, void *sink, lvlip_lro_result *gate,
+                   lvlip_rbuf_result *rres);
+
 /* RFC 1071 pseudo-header seed with the carries folded back (for RX verify of
  * checksums produced by RFC-correct peers). */
 uint32_t lvlip_pseudo_sum_rfc(uint32_t saddr, uint32_t daddr, uint8_t proto,

@@ -1,10 +1,11 @@
 /*
  * flow_step.h — one flow's step of the protocol state machines, once for both
  * sides: the retransmission timer, the congestion window, the peer's window,
- * the push count, the class of an ACK and the persist timer.  The CPU forms
- * (rto_cpu.c, cc_cpu.c, push_cpu.c, snd_cpu.c, persist_cpu.c) call these on the
- * flow in the caller's array, the kernels (rto_, cc_, push_, snd_ and
- * persist_kernels.hip) on a flow in registers.
+ * the push count, the class of an ACK, the persist timer and the receive
+ * buffer.  The CPU forms (rto_cpu.c, cc_cpu.c, push_cpu.c, snd_cpu.c,
+ * persist_cpu.c, rbuf_cpu.c) call these on the flow in the caller's array, the
+ * kernels (rto_, cc_, push_, snd_ and persist_kernels.hip) on a flow in
+ * registers; the receive buffer has no kernel yet.
  * Every function takes scalars and one flow; none sees a batch.  How a flow's
  * words travel between HBM and registers, which lane runs the step and what is
  * reduced around it stays in the kernels.  Plain C99, not installed.
@@ -229,6 +230,69 @@ FLOW_FN flow_persist_out flow_persist_step(lvlip_persist_flow *x, uint32_t dead,
         x->expires = now + x->interval;
     }
     o.interval = x->interval, o.probes = x->probes;
+    return o;
+}
+
+typedef struct flow_rbuf_out {
+    uint32_t read, unread, moved, adv, field, flags; /* lvlip_rbuf_result's; head is x->head */
+    uint32_t rd_from;                                /* the read's source, from base_off; its length is `read` */
+    uint32_t mv_from;                                /* the move's source, from base_off; its length is `moved` */
+    uint64_t rd_to;                                  /* the read's destination, from the sink base */
+} flow_rbuf_out;
+
+/* step 2's largest right edge so far, with block b if it is reported and counts
+ * (constant indices at the call: a kernel keeps the blocks in registers) */
+FLOW_FN uint32_t flow_rbuf_span(uint32_t span, lvlip_lro_sack b, int reported, uint32_t rcv_nxt, uint32_t rcv_wnd)
+{
+    const uint32_t l = b.left - rcv_nxt, r = b.right - rcv_nxt;
+    return reported && l < r && r <= rcv_wnd && r > span ? r : span;
+}
+
+/* Steps 1-4 of lvlip_rbuf_* and step 5's verdict on *x, for a flow whose
+ * region starts at *out_off with *rcv_wnd bytes and wants rcv_nxt, whose
+ * application asks for nread bytes (into a sink or not) and whose last result
+ * has the islands sack[0 .. nsack) and `placed` frames.  For a state
+ * lvlip_rbuf_check accepts used <= cap and head <= used; a block counts only
+ * when it ends inside rcv_wnd, so head + live <= cap whatever the islands say:
+ * both copies stay inside the flow's buffer. */
+FLOW_FN flow_rbuf_out flow_rbuf_step(lvlip_rbuf_flow *x, uint64_t *out_off, uint32_t *rcv_wnd, uint32_t rcv_nxt,
+                                     uint32_t nread, uint32_t have_sink, const lvlip_lro_sack *sack, uint32_t nsack,
+                                     uint32_t placed)
+{
+    flow_rbuf_out o = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    const uint32_t used = (uint32_t)(*out_off - x->base_off);
+    /* 1: read (tcp_data_dequeue's copy, src/tcp_data.c:49-85) */
+    const uint32_t unread = used - x->head;
+    o.read = nread < unread ? nread : unread;
+    o.rd_from = x->head, o.rd_to = x->sink_off;
+    if (have_sink) x->sink_off += o.read;
+    x->head += o.read;
+    o.unread = used - x->head;
+    /* 2: live bytes, the carried blocks under lvlip_lro_advance_carry's rule */
+    uint32_t span = 0;
+    span = flow_rbuf_span(span, sack[0], nsack > 0u, rcv_nxt, *rcv_wnd);
+    span = flow_rbuf_span(span, sack[1], nsack > 1u, rcv_nxt, *rcv_wnd);
+    span = flow_rbuf_span(span, sack[2], nsack > 2u, rcv_nxt, *rcv_wnd);
+    span = flow_rbuf_span(span, sack[3], nsack > 3u, rcv_nxt, *rcv_wnd);
+    const uint64_t live = (uint64_t)o.unread + span;
+    /* 3: reuse */
+    if (x->head > 0u && live <= x->head) {
+        o.moved = (uint32_t)live, o.mv_from = x->head;
+        *out_off -= x->head, *rcv_wnd += x->head;
+        x->head = 0u;
+        o.flags |= LVLIP_RBUF_MOVED;
+    }
+    /* 4: window (RFC 1122 4.2.3.3, Fr = 1/2; RFC 793: the edge never moves left) */
+    const uint32_t edge = rcv_nxt + *rcv_wnd;
+    const uint32_t half = x->cap / 2u + (x->cap & 1u);
+    if ((uint32_t)(edge - x->adv_edge) >= (half < x->mss ? half : x->mss)) {
+        x->adv_edge = edge;
+        o.flags |= LVLIP_RBUF_ADVANCED;
+        if (placed == 0u) o.flags |= LVLIP_RBUF_UPDATE; /* 5 */
+    }
+    o.adv = x->adv_edge - rcv_nxt;
+    const uint32_t fld = o.adv >> (x->wscale & 15u);
+    o.field = fld < 65535u ? fld : 65535u;
     return o;
 }
 

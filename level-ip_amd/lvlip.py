@@ -272,6 +272,10 @@ SIGNATURES = {
     "lvlip_persist_check": (_INT, [_P, _U32]),
     "lvlip_persist_cpu": (_INT, [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P]),
     "lvlip_persist_dev": (_INT, [_P, _P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P]),
+    # f1: the receive buffer (rbuf_cpu.c)
+    "lvlip_rbuf_plan": (_U32, [_P, _P, _U32, ctypes.POINTER(ctypes.c_uint64)]),
+    "lvlip_rbuf_check": (_INT, [_P, _P, _U32]),
+    "lvlip_rbuf_cpu": (_INT, [_P, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),
     "lvlip_auto_kernel": (_INT, [_I32, _U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (_U32, [_U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (_STR, []),
@@ -1597,6 +1601,85 @@ def persist_dev(flows_t, lro_res_t, snd_t, push_t, rto_t, persist_t, now: int, o
                                   rto_t.data_ptr(), persist_t.data_ptr(), nflows, now & 0xFFFFFFFF, out_t.data_ptr(),
                                   fd_out_t.data_ptr(), res_t.data_ptr(), s.cuda_stream), "lvlip_persist_dev")
     return fd_out_t[:16 * nflows], res_t[:PERSIST_RESULT_DTYPE.itemsize * nflows]
+
+
+# ------------------------------------------------------ f1: the receive buffer --
+
+# struct lvlip_rbuf_flow (48 B) / lvlip_rbuf_result (32 B), include/lvlip_skb.h
+RBUF_FLOW_DTYPE = np.dtype([("base_off", "<u8"), ("sink_off", "<u8"), ("cap", "<u4"), ("head", "<u4"),
+                            ("adv_edge", "<u4"), ("piece0", "<u4"), ("mss", "<u2"), ("wscale", "u1"),
+                            ("reserved", "u1", (13,))])
+RBUF_RESULT_DTYPE = np.dtype([("read", "<u4"), ("unread", "<u4"), ("head", "<u4"), ("moved", "<u4"), ("adv", "<u4"),
+                              ("field", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+RBUF_PIECE = 16384
+RBUF_MOVED, RBUF_ADVANCED, RBUF_UPDATE = 1, 2, 4
+assert RBUF_FLOW_DTYPE.itemsize == 48 and RBUF_RESULT_DTYPE.itemsize == 32
+
+
+def rbuf_flows(flows: np.ndarray, mss: int, wscale: int = 0, sink_off=0) -> np.ndarray:
+    """Fresh lvlip_rbuf_flow states for the planned flows: the buffer is the
+    flow's region as it stands, nothing read, the whole window advertised.
+    sink_off: one offset per flow (or one for all).  Not yet planned."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    p = np.zeros(flows.size, dtype=RBUF_FLOW_DTYPE)
+    p["base_off"], p["cap"] = flows["out_off"], flows["rcv_wnd"]
+    p["adv_edge"] = flows["rcv_nxt"] + flows["rcv_wnd"]
+    p["mss"], p["wscale"], p["sink_off"] = mss, wscale, sink_off
+    return p
+
+
+def rbuf_plan(rbuf: np.ndarray, flows: np.ndarray) -> int:
+    """lvlip_rbuf_plan: validates the states against the planned flows and
+    writes piece0 IN PLACE.  Returns the number of copy pieces; ValueError for
+    a refused plan."""
+    _planned(rbuf, RBUF_FLOW_DTYPE, "rbuf: a writeable contiguous RBUF_FLOW_DTYPE array")
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    if rbuf.size != flows.size:
+        raise ValueError("one buffer state per flow")
+    npieces = ctypes.c_uint64(0)
+    _plan_ok(int(_lib.lvlip_rbuf_plan(_aptr(rbuf), _aptr(flows), flows.size, ctypes.byref(npieces))),
+             "refused buffer states (an invariant against the flow, cap, mss, wscale, reserved, overlapping "
+             "buffers, too many)")
+    return int(npieces.value)
+
+
+def rbuf_check(rbuf: np.ndarray, flows: np.ndarray) -> None:
+    """lvlip_rbuf_check: ValueError for a state the calls refuse."""
+    _planned(rbuf, RBUF_FLOW_DTYPE, "rbuf: a contiguous RBUF_FLOW_DTYPE array", writeable=False)
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    if rbuf.size != flows.size:
+        raise ValueError("one buffer state per flow")
+    rc = _lib.lvlip_rbuf_check(_aptr(rbuf), _aptr(flows), flows.size)
+    if rc == EINVAL:
+        raise ValueError("refused buffer state (an invariant against the flow, piece0, cap, mss, wscale, reserved, "
+                         "overlapping buffers, too many)")
+    _check(rc, "lvlip_rbuf_check")
+
+
+def rbuf_cpu(flows: np.ndarray, res: np.ndarray, rbuf: np.ndarray, tmpl: np.ndarray, nread, out: np.ndarray,
+             sink: Optional[np.ndarray] = None):
+    """lvlip_rbuf_cpu: one round of the receive buffer, IN PLACE in flows
+    (out_off, rcv_wnd), rbuf, tmpl (the window field), out (the moved bytes)
+    and sink (the bytes read; None drops them).  res (LRO_RESULT_DTYPE) as
+    lro_next_* left it; nread: uint32 per flow, or None for 0.  Returns (gate,
+    rres): LRO_RESULT_DTYPE for ack_*, and RBUF_RESULT_DTYPE per flow."""
+    _planned(flows, LRO_FLOW_DTYPE, "flows: a writeable contiguous LRO_FLOW_DTYPE array")
+    _planned(rbuf, RBUF_FLOW_DTYPE, "rbuf: a writeable contiguous RBUF_FLOW_DTYPE array")
+    _planned(tmpl, ACK_TMPL_DTYPE, "tmpl: a writeable contiguous ACK_TMPL_DTYPE array")
+    res = np.ascontiguousarray(res, dtype=LRO_RESULT_DTYPE)
+    n = flows.size
+    if nread is not None:
+        nread = np.ascontiguousarray(nread, dtype=np.uint32)
+    if any(a.size != n for a in (res, rbuf, tmpl)) or (nread is not None and nread.size != n):
+        raise ValueError("one result, buffer state, template and read count per flow")
+    for a, what in ((out, "out"), (sink, "sink")):
+        if a is not None and not _is_u8(a, writeable=True):
+            raise ValueError(f"{what}: a writeable contiguous uint8 array")
+    gate = np.zeros(n, dtype=LRO_RESULT_DTYPE)
+    rres = np.zeros(n, dtype=RBUF_RESULT_DTYPE)
+    _check(_lib.lvlip_rbuf_cpu(_aptr(flows), _aptr(res), _aptr(rbuf), _aptr(tmpl), n, _aptr(nread), _aptr(out),
+                               _aptr(sink), _aptr(gate), _aptr(rres)), "lvlip_rbuf_cpu")
+    return gate, rres
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
