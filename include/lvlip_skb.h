@@ -332,7 +332,8 @@ int lvlip_tso_dev(const void *payload, const lvlip_tso_send *s, uint32_t n, uint
  *   NO_DATA        dlen == 0 (a pure ACK, a bare FIN); rel and ack_seq are valid
  *   OUT_OF_WINDOW  rel + dlen > rcv_wnd in 64-bit arithmetic
  *   PLACED         the dlen payload bytes are at out + out_off + rel.  FIN with
- *                  data is placed; the host sees FIN in tcp_flags.
+ *                  data is placed; FIN is in tcp_flags, where lvlip_fin_*
+ *                  ("the end of a connection") reads it.
  * IPv4 and TCP options are accepted and skipped.
  *
  * The bytes of `out`.  After the call the dlen bytes at out + out_off + rel
@@ -1036,8 +1037,9 @@ int lvlip_rtx_sack_dev(const lvlip_lro_flow *f, const lvlip_lro_result *lro, con
  * after a compaction.  Refilling pay_off / unsent / wnd is the application's
  * step, as reopening rcv_wnd is.  wnd is the hook for a peer's or a congestion
  * window: the reference never limits the bytes in flight (snd_wnd is written
- * once, src/tcp_output.c:429); 2^30 means "no limit".  A FIN would have to
- * advance snd_nxt: that stays with the caller, and the plan refuses it. */
+ * once, src/tcp_output.c:429); 2^30 means "no limit".  A FIN has to
+ * advance snd_nxt: the plan refuses it in a template, and lvlip_fin_* below
+ * ("the end of a connection") sends it once `unsent` is 0. */
 typedef struct lvlip_push_flow {      /* one per planned flow; sizeof == 112 */
     uint64_t pay_off;                 /* the next unsent byte, from the payload base; any alignment */
     uint64_t ring_off;                /* frame slot 0, from the ring base; any alignment */
@@ -1502,7 +1504,7 @@ int lvlip_cc_dev(const lvlip_snd_flow *s, const lvlip_snd_result *snd, const lvl
  * under LVLIP_ACK_ALL; RFC 793 says an unacceptable segment elicits an ACK, and
  * arranging that is the receiving caller's step.  Also out of scope: the
  * one-byte BSD probe, sender-side SWS override timers, advertising rcv_wnd
- * from the device, FIN. */
+ * from the device.  FIN is lvlip_fin_* below ("the end of a connection"). */
 #define LVLIP_PERSIST_MAX_MS 60000u
 #define LVLIP_PERSIST_SLOT   64u      /* probe k is the 54 bytes at out + 64 k */
 
@@ -1670,6 +1672,186 @@ int lvlip_rbuf_check(const lvlip_rbuf_flow *p, const lvlip_lro_flow *f, uint32_t
 int lvlip_rbuf_cpu(lvlip_lro_flow *f, const lvlip_lro_result *res, lvlip_rbuf_flow *p, lvlip_ack_tmpl *t,
                    uint32_t nflows, const uint32_t *nread, void *out, void *sink, lvlip_lro_result *gate,
                    lvlip_rbuf_result *rres);
+
+/* ---- the end of a connection: FIN and TIME-WAIT ------------------------------ */
+
+/* What ends a connection in the reference: tcp_close -> tcp_queue_fin
+ * (src/tcp.c:255-285, src/tcp_output.c:506-523), the fifth and the eighth check
+ * of tcp_input_state (src/tcp_input.c:359-389, :417-467) and
+ * tcp_enter_time_wait (src/tcp.c:402-411).  lvlip_fin_* is that state machine
+ * per planned flow and round: it sees the peer's FIN in the round's records,
+ * sends this host's FIN once the application has asked for it and everything
+ * written has been segmented, re-sends it on a timer of its own, follows the
+ * states of RFC 793 down to CLOSED and owes the ACK of the peer's FIN through
+ * the `gate` mechanism of lvlip_rbuf_* above.
+ *
+ * lvlip_fin_flow k belongs to connection k: f[k] is its receive side, s[k],
+ * w[k] and t[k] its send side, write side and retransmission timer (the
+ * forward and the reverse plan of one endpoint list the connections in the
+ * same order).  A fresh flow is {base = f[k].rcv_nxt, state =
+ * LVLIP_TCP_ESTABLISHED, the rest 0}.  The struct has no padding.
+ *
+ * Where it sits in the loop.  Once per round at each endpoint: after the
+ * round's lvlip_lro_* -> lvlip_lro_advance_carry* -> lvlip_lro_next_* (and
+ * lvlip_rbuf_* where used), after lvlip_snd_next_*, lvlip_push_*, lvlip_rto_*
+ * and lvlip_persist_*, with the `now` these got; before lvlip_ack_*, which is
+ * given `gate` as its res, and before the retransmit.  rec are the round's
+ * records, gin is the result lvlip_ack_* would have been given.
+ *
+ * One call, for flow k, from the values at entry, in this fixed order:
+ *   0 dead or closed.  t[k].dead set or x.state == LVLIP_TCP_CLOSED: x.base =
+ *              f.rcv_nxt and nothing else of x changes; gate[k] = gin[k],
+ *              fd_out[k] = {64 k, 0, 0}, res[k] = {0, x.state, 0, 0}, no byte
+ *              of out.
+ *   1 FIN records.  A record counts for flow k when rec.flow == k, its status
+ *              is PLACED or NO_DATA and tcp_flags & 0x01; its key is (rel +
+ *              dlen) mod 2^32, the stream offset of the FIN from x.base.
+ *              target = (f.rcv_nxt + gin.delivered - x.base) mod 2^32 is where
+ *              the stream stands now, whether lvlip_lro_next_* has run or not.
+ *              hit: some record has key == target.  again: some record has
+ *              key == target - 1, a FIN already counted.  Nothing is kept
+ *              across rounds: a FIN in front of a hole is ignored and the
+ *              peer sends it again, as the reference's `th->fin && expected`
+ *              (src/tcp_input.c:418) has it; a FIN whose hole the same batch
+ *              fills IS taken, which the reference, a frame at a time, would
+ *              not do.
+ *   2 our FIN acknowledged.  x.state FIN_WAIT_1, CLOSING or LAST_ACK and
+ *              s.snd_una == x.fin_seq + 1: ACKED.  FIN_WAIT_1 -> FIN_WAIT_2;
+ *              CLOSING -> TIME_WAIT with interval = LVLIP_FIN_2MSL_MS and
+ *              expires = now + interval (TCP_2MSL, src/tcp.c:410); LAST_ACK ->
+ *              CLOSED.
+ *   3 the peer's FIN.  hit in ESTABLISHED, FIN_WAIT_1 or FIN_WAIT_2:
+ *              f[k].rcv_nxt += 1, PEER_FIN | ACK_OWED; ESTABLISHED ->
+ *              CLOSE_WAIT, FIN_WAIT_1 -> CLOSING, FIN_WAIT_2 -> TIME_WAIT,
+ *              armed as in step 2.  A FIN_WAIT_1 flow with hit and ACKED in
+ *              one call so ends in TIME_WAIT (src/tcp_input.c:441-449).
+ *              again in CLOSE_WAIT, CLOSING, LAST_ACK or TIME_WAIT: ACK_OWED,
+ *              and TIME_WAIT starts its timer afresh (RFC 793; a TODO at
+ *              src/tcp_input.c:463).
+ *   4 close.   close[k] != 0 (close may be NULL) sets LVLIP_FIN_CLOSE_REQ in
+ *              x.flags, where it stays.  With it, in ESTABLISHED or CLOSE_WAIT
+ *              and with w.unsent == 0: fin_seq = s.snd_nxt, s[k].snd_nxt += 1,
+ *              ESTABLISHED -> FIN_WAIT_1, CLOSE_WAIT -> LAST_ACK, interval =
+ *              max(1, min(t.rto, 60000)), expires = now + interval, retries =
+ *              0, SENT, and the frame below is written.  Data may still be in
+ *              flight: the FIN follows the last segment on the wire.
+ *   5 timers, for a flow that did not send in step 4.  In FIN_WAIT_1, CLOSING
+ *              or LAST_ACK: with s.nseg > 0 the timer is held at expires =
+ *              now + interval (the data's timer is lvlip_rto_*'s); otherwise,
+ *              if expires < now (strict and unsigned, the test of
+ *              lvlip_persist_* step 4) the frame is written again, retries +=
+ *              1 (it stops at 2^32 - 1), interval = min(2 * interval, 60000)
+ *              formed in 64 bits, expires = now + interval, RESENT.  In
+ *              TIME_WAIT, expires < now: CLOSED, TW_DONE.
+ *   6 stores.  x.base = f.rcv_nxt.  gate[k] = all 48 bytes of gin[k], with
+ *              placed = 1 when ACK_OWED is set and gin.placed == 0: the
+ *              unchanged lvlip_ack_* without LVLIP_ACK_ALL then sends the ACK
+ *              of the FIN (ack_seq = rcv_nxt + delivered covers it).  res[k] =
+ *              {events, x.state, the frame's seq or 0, x.interval}.
+ *              LATE_WRITE is set when the flow ends the call in FIN_WAIT_1,
+ *              FIN_WAIT_2, CLOSING, LAST_ACK or TIME_WAIT with w.unsent > 0: a
+ *              write behind our FIN.  It is reported; nothing is done.
+ *
+ * The frame is the 54 bytes at out + 64 k, lvlip_persist_*'s slot and writer:
+ * w[k].hdr with total length htons(40), both checksums as there, window =
+ * htons(s[k].win), seq = htonl(x.fin_seq), ack_seq = htonl(f.rcv_nxt +
+ * gin.delivered) as step 3 left rcv_nxt, and byte 13 the template's with PSH
+ * cleared and FIN and ACK set: what tcp_queue_fin leaves there
+ * (src/tcp_output.c:515-516).  fd_out[k] = {64 k, 54, 0}, or {64 k, 0, 0} and
+ * no byte of out when no frame is written.  Bytes 54 .. 63 of a slot are never
+ * written.
+ *
+ * Only f[k].rcv_nxt, s[k].snd_nxt, x, gate, res, fd_out and the frames are
+ * written.  The FIN is no queue entry: nseg, `popped` and the scoreboard never
+ * see it, and with span = snd_nxt - snd_una = 1 its ACK classes as new in
+ * lvlip_snd_*.
+ *
+ * Departures from the reference.  tcp_close leaves a CLOSE_WAIT socket in
+ * CLOSE_WAIT (src/tcp.c:278-282); here it enters LAST_ACK, as RFC 793 has it.
+ * The reference takes an empty write queue for "our FIN was acknowledged" and
+ * enters TIME_WAIT from CLOSING without a timer (src/tcp_input.c:360-371);
+ * here the test is on snd_una and the timer is armed.  The FIN's timer is this
+ * call's own: lvlip_rto_* stops with the empty queue.  lvlip_cc_* sees one
+ * acknowledged byte more than was sent as data.  The sequence number on the
+ * ACKs lvlip_ack_* builds is the template's: after SENT the caller's template
+ * has to carry fin_seq + 1. */
+#define LVLIP_TCP_ESTABLISHED 3u      /* x.state: the numbers of the reference's enum tcp_states */
+#define LVLIP_TCP_FIN_WAIT_1  4u
+#define LVLIP_TCP_FIN_WAIT_2  5u
+#define LVLIP_TCP_CLOSED      6u
+#define LVLIP_TCP_CLOSE_WAIT  7u
+#define LVLIP_TCP_CLOSING     8u
+#define LVLIP_TCP_LAST_ACK    9u
+#define LVLIP_TCP_TIME_WAIT   10u
+#define LVLIP_FIN_CLOSE_REQ   0x1u    /* x.flags: the application has closed; sticky */
+#define LVLIP_FIN_MAX_MS      60000u  /* the ceiling of the FIN's interval */
+#define LVLIP_FIN_2MSL_MS     60000u  /* TCP_2MSL, include/tcp.h:32 */
+#define LVLIP_FIN_EV_PEER_FIN   0x01u /* res.events */
+#define LVLIP_FIN_EV_ACK_OWED   0x02u
+#define LVLIP_FIN_EV_SENT       0x04u
+#define LVLIP_FIN_EV_RESENT     0x08u
+#define LVLIP_FIN_EV_ACKED      0x10u
+#define LVLIP_FIN_EV_TW_DONE    0x20u
+#define LVLIP_FIN_EV_LATE_WRITE 0x40u
+
+typedef struct lvlip_fin_flow {       /* one per connection; sizeof == 32, no padding */
+    uint32_t base;                    /* f[k].rcv_nxt as the last call left it */
+    uint32_t fin_seq;                 /* host order: the sequence number of our FIN */
+    uint32_t expires;                 /* the running timer's deadline (FIN re-send or 2 MSL) */
+    uint32_t interval;                /* ms, 0 .. 60000 */
+    uint32_t retries;                 /* FIN re-sends so far; saturates */
+    uint8_t  state;                   /* LVLIP_TCP_* */
+    uint8_t  flags;                   /* LVLIP_FIN_CLOSE_REQ */
+    uint8_t  reserved[10];            /* 0 */
+} lvlip_fin_flow;
+
+typedef struct lvlip_fin_result {     /* one per connection; sizeof == 16 */
+    uint32_t events, state, seq, interval;
+} lvlip_fin_result;
+
+/* Host only, between rounds: 0 when every x[k] is a state these calls take and
+ * x[k].base == f[k].rcv_nxt (every call leaves that), LVLIP_EINVAL for a state
+ * that is no LVLIP_TCP_* value, nonzero reserved bytes, an interval above
+ * 60000, a base that is not f[k].rcv_nxt, a NULL x or f with nflows > 0 or
+ * nflows above LVLIP_LRO_MAX_FLOWS.  Nothing is written. */
+int lvlip_fin_check(const lvlip_fin_flow *x, const lvlip_lro_flow *f, uint32_t nflows);
+
+/* On the calling thread, the frame through the writer lvlip_persist_cpu uses.
+ * gin, rec (may be NULL with n == 0), w, t and close (may be NULL) are read; f,
+ * s, x, out (64 bytes per flow, any alignment), fd_out, gate and res are
+ * written as above.  gate must not be gin.  Returns 0, or LVLIP_EINVAL with
+ * nothing written: NULL f, gin, s, w, t, x, out, fd_out, gate or res with
+ * nflows > 0, NULL rec with n > 0, gate == gin, nflows above
+ * LVLIP_LRO_MAX_FLOWS, n above LVLIP_MAX_BATCH, or an x lvlip_fin_check would
+ * refuse for its state, reserved bytes or interval (base is not tested: inside
+ * a round rcv_nxt has moved on).  nflows == 0 is a no-op.  Reentrant. */
+int lvlip_fin_cpu(lvlip_lro_flow *f, const lvlip_lro_result *gin, const lvlip_lro_rec *rec, uint32_t n,
+                  lvlip_snd_flow *s, const lvlip_push_flow *w, const lvlip_rto_flow *t, lvlip_fin_flow *x,
+                  uint32_t nflows, const uint8_t *close, uint32_t now, void *out, lvlip_frame_desc *fd_out,
+                  lvlip_lro_result *gate, lvlip_fin_result *res);
+
+/* Bytes of workspace lvlip_fin_dev needs for nflows connections: two bytes per
+ * flow, in whole 16-B units, at least 16. */
+size_t lvlip_fin_workspace_bytes(uint32_t nflows);
+
+/* The same bytes on the caller's stream (asynchronous; no allocation, copy,
+ * atomics, LDS or synchronisation): the workspace is cleared with a memset on
+ * the stream, a lane per record marks its flow's `hit` or `again` byte (plain
+ * stores of the constant 1), and eight lanes per flow run the steps, build
+ * the 54 bytes in registers and each keep one aligned 16-byte chunk of the
+ * frame; the first lane stores x[k], res[k], fd_out[k], gate[k] and, only when
+ * they change, the four bytes of f[k].rcv_nxt and of s[k].snd_nxt.  All
+ * pointers are device pointers: f, s, w, t and x 8-B aligned, gin, rec, fd_out,
+ * gate, res and ws 16-B aligned, close and out any alignment; ws holds
+ * lvlip_fin_workspace_bytes(nflows) bytes and its contents afterwards are
+ * unspecified.  The NULL and limit refusals of lvlip_fin_cpu, a NULL ws and a
+ * misaligned pointer are LVLIP_EINVAL before any HIP call (x is not looked at:
+ * the caller checked it); LVLIP_ENODEV without a device; a failed launch is
+ * LVLIP_EHIP (lvlip_last_hip_error).  Measured: DESIGN.md section 9o. */
+int lvlip_fin_dev(lvlip_lro_flow *f, const lvlip_lro_result *gin, const lvlip_lro_rec *rec, uint32_t n,
+                  lvlip_snd_flow *s, const lvlip_push_flow *w, const lvlip_rto_flow *t, lvlip_fin_flow *x,
+                  uint32_t nflows, const uint8_t *close, uint32_t now, void *out, lvlip_frame_desc *fd_out,
+                  lvlip_lro_result *gate, lvlip_fin_result *res, void *ws, void *stream);
 
 /* RFC 1071 pseudo-header seed with the carries folded back (for RX verify of
  * checksums produced by RFC-correct peers). */

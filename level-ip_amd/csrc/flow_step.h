@@ -1,11 +1,12 @@
 /*
  * flow_step.h — one flow's step of the protocol state machines, once for both
  * sides: the retransmission timer, the congestion window, the peer's window,
- * the push count, the class of an ACK, the persist timer and the receive
- * buffer.  The CPU forms (rto_cpu.c, cc_cpu.c, push_cpu.c, snd_cpu.c,
- * persist_cpu.c, rbuf_cpu.c) call these on the flow in the caller's array, the
- * kernels (rto_, cc_, push_, snd_ and persist_kernels.hip) on a flow in
- * registers; the receive buffer has no kernel yet.
+ * the push count, the class of an ACK, the persist timer, the receive buffer
+ * and the connection's close.  The CPU forms (rto_cpu.c, cc_cpu.c, push_cpu.c,
+ * snd_cpu.c, persist_cpu.c, rbuf_cpu.c, fin_cpu.c) call these on the flow in
+ * the caller's array, the kernels (rto_, cc_, push_, snd_, persist_ and
+ * fin_kernels.hip) on a flow in registers; the receive buffer has no kernel
+ * yet.
  * Every function takes scalars and one flow; none sees a batch.  How a flow's
  * words travel between HBM and registers, which lane runs the step and what is
  * reduced around it stays in the kernels.  Plain C99, not installed.
@@ -293,6 +294,101 @@ FLOW_FN flow_rbuf_out flow_rbuf_step(lvlip_rbuf_flow *x, uint64_t *out_off, uint
     o.adv = x->adv_edge - rcv_nxt;
     const uint32_t fld = o.adv >> (x->wscale & 15u);
     o.field = fld < 65535u ? fld : 65535u;
+    return o;
+}
+
+typedef struct flow_fin_out {
+    uint32_t events;  /* LVLIP_FIN_EV_* */
+    uint32_t frame;   /* 0 or 1: the FIN goes out, with sequence number x->fin_seq */
+    uint32_t rcv_nxt; /* the receive side's rcv_nxt as step 3 leaves it */
+    uint32_t snd_nxt; /* the send side's snd_nxt as step 4 leaves it */
+    uint32_t interval; /* lvlip_fin_result's interval: 0 from step 0 */
+} flow_fin_out;
+
+/* our FIN is out and the connection is not yet over */
+FLOW_FN int flow_fin_sent(uint32_t state)
+{
+    return state == LVLIP_TCP_FIN_WAIT_1 || state == LVLIP_TCP_FIN_WAIT_2 || state == LVLIP_TCP_CLOSING ||
+           state == LVLIP_TCP_LAST_ACK || state == LVLIP_TCP_TIME_WAIT;
+}
+
+/* Steps 0 and 2-5 of lvlip_fin_* on *x and step 6's x.base, for a connection
+ * whose receive side wants rcv_nxt, whose send side stands at snd_una ..
+ * snd_nxt with nseg queue entries and `unsent` bytes not yet segmented, whose
+ * retransmission timer stands at rto (and is dead or not), whose records of
+ * this round hold the peer's FIN at the stream's end (hit) or one byte before
+ * it (again), and whose application has closed or not, at time now. */
+FLOW_FN flow_fin_out flow_fin_step(lvlip_fin_flow *x, uint32_t dead, uint32_t rcv_nxt, uint32_t snd_una,
+                                   uint32_t snd_nxt, uint32_t nseg, uint32_t unsent, uint32_t rto, uint32_t hit,
+                                   uint32_t again, uint32_t close, uint32_t now)
+{
+    flow_fin_out o = {0u, 0u, rcv_nxt, snd_nxt, 0u};
+    x->base = rcv_nxt;
+    if (dead || x->state == LVLIP_TCP_CLOSED) return o; /* 0 */
+    uint32_t st = x->state;
+    /* 2: our FIN acknowledged (src/tcp_input.c:359-376) */
+    if ((st == LVLIP_TCP_FIN_WAIT_1 || st == LVLIP_TCP_CLOSING || st == LVLIP_TCP_LAST_ACK) &&
+        snd_una == x->fin_seq + 1u) {
+        o.events |= LVLIP_FIN_EV_ACKED;
+        if (st == LVLIP_TCP_FIN_WAIT_1) {
+            st = LVLIP_TCP_FIN_WAIT_2;
+        } else if (st == LVLIP_TCP_CLOSING) {
+            st = LVLIP_TCP_TIME_WAIT;
+            x->interval = LVLIP_FIN_2MSL_MS, x->expires = now + LVLIP_FIN_2MSL_MS; /* src/tcp.c:410 */
+        } else {
+            st = LVLIP_TCP_CLOSED;
+        }
+    }
+    /* 3: the peer's FIN (src/tcp_input.c:417-467) */
+    if (hit && (st == LVLIP_TCP_ESTABLISHED || st == LVLIP_TCP_FIN_WAIT_1 || st == LVLIP_TCP_FIN_WAIT_2)) {
+        o.rcv_nxt = rcv_nxt + 1u; /* :429 */
+        o.events |= LVLIP_FIN_EV_PEER_FIN | LVLIP_FIN_EV_ACK_OWED;
+        if (st == LVLIP_TCP_ESTABLISHED) {
+            st = LVLIP_TCP_CLOSE_WAIT;
+        } else if (st == LVLIP_TCP_FIN_WAIT_1) {
+            st = LVLIP_TCP_CLOSING;
+        } else {
+            st = LVLIP_TCP_TIME_WAIT;
+            x->interval = LVLIP_FIN_2MSL_MS, x->expires = now + LVLIP_FIN_2MSL_MS;
+        }
+    }
+    if (again && (st == LVLIP_TCP_CLOSE_WAIT || st == LVLIP_TCP_CLOSING || st == LVLIP_TCP_LAST_ACK ||
+                  st == LVLIP_TCP_TIME_WAIT)) {
+        o.events |= LVLIP_FIN_EV_ACK_OWED;
+        if (st == LVLIP_TCP_TIME_WAIT) x->interval = LVLIP_FIN_2MSL_MS, x->expires = now + LVLIP_FIN_2MSL_MS;
+    }
+    x->base = o.rcv_nxt;
+    /* 4: close (tcp_close, src/tcp.c:271-282; tcp_queue_fin) */
+    if (close) x->flags |= (uint8_t)LVLIP_FIN_CLOSE_REQ;
+    if ((x->flags & LVLIP_FIN_CLOSE_REQ) && (st == LVLIP_TCP_ESTABLISHED || st == LVLIP_TCP_CLOSE_WAIT) &&
+        unsent == 0u) {
+        const uint32_t iv = rto < LVLIP_FIN_MAX_MS ? rto : LVLIP_FIN_MAX_MS;
+        x->fin_seq = snd_nxt;
+        o.snd_nxt = snd_nxt + 1u; /* src/tcp_output.c:150 */
+        st = st == LVLIP_TCP_ESTABLISHED ? LVLIP_TCP_FIN_WAIT_1 : LVLIP_TCP_LAST_ACK;
+        x->interval = iv ? iv : 1u;
+        x->expires = now + x->interval;
+        x->retries = 0u;
+        o.events |= LVLIP_FIN_EV_SENT;
+        o.frame = 1u;
+    } else if (st == LVLIP_TCP_FIN_WAIT_1 || st == LVLIP_TCP_CLOSING || st == LVLIP_TCP_LAST_ACK) { /* 5 */
+        if (nseg > 0u) {
+            x->expires = now + x->interval;
+        } else if (x->expires < now) { /* src/timer.c:71, as flow_persist_step */
+            const uint64_t twice = 2ull * x->interval;
+            if (x->retries != 0xFFFFFFFFu) x->retries++;
+            x->interval = twice < LVLIP_FIN_MAX_MS ? (uint32_t)twice : LVLIP_FIN_MAX_MS;
+            x->expires = now + x->interval;
+            o.events |= LVLIP_FIN_EV_RESENT;
+            o.frame = 1u;
+        }
+    } else if (st == LVLIP_TCP_TIME_WAIT && x->expires < now) {
+        st = LVLIP_TCP_CLOSED;
+        o.events |= LVLIP_FIN_EV_TW_DONE;
+    }
+    if (flow_fin_sent(st) && unsent > 0u) o.events |= LVLIP_FIN_EV_LATE_WRITE;
+    x->state = (uint8_t)st;
+    o.interval = x->interval;
     return o;
 }
 

@@ -276,6 +276,11 @@ SIGNATURES = {
     "lvlip_rbuf_plan": (_U32, [_P, _P, _U32, ctypes.POINTER(ctypes.c_uint64)]),
     "lvlip_rbuf_check": (_INT, [_P, _P, _U32]),
     "lvlip_rbuf_cpu": (_INT, [_P, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),
+    # the end of a connection (fin_cpu.c, fin_kernels.hip)
+    "lvlip_fin_check": (_INT, [_P, _P, _U32]),
+    "lvlip_fin_cpu": (_INT, [_P, _P, _P, _U32, _P, _P, _P, _P, _U32, _P, _U32, _P, _P, _P, _P]),
+    "lvlip_fin_workspace_bytes": (_SZ, [_U32]),
+    "lvlip_fin_dev": (_INT, [_P, _P, _P, _U32, _P, _P, _P, _P, _U32, _P, _U32, _P, _P, _P, _P, _P, _P]),
     "lvlip_auto_kernel": (_INT, [_I32, _U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_batch_launches": (_U32, [_U32, ctypes.POINTER(LaunchCfg)]),
     "lvlip_build_id": (_STR, []),
@@ -1680,6 +1685,108 @@ def rbuf_cpu(flows: np.ndarray, res: np.ndarray, rbuf: np.ndarray, tmpl: np.ndar
     _check(_lib.lvlip_rbuf_cpu(_aptr(flows), _aptr(res), _aptr(rbuf), _aptr(tmpl), n, _aptr(nread), _aptr(out),
                                _aptr(sink), _aptr(gate), _aptr(rres)), "lvlip_rbuf_cpu")
     return gate, rres
+
+
+# ------------------------------------------------- the end of a connection --
+
+# struct lvlip_fin_flow (32 B) / lvlip_fin_result (16 B), include/lvlip_skb.h
+FIN_FLOW_DTYPE = np.dtype([("base", "<u4"), ("fin_seq", "<u4"), ("expires", "<u4"), ("interval", "<u4"),
+                           ("retries", "<u4"), ("state", "u1"), ("flags", "u1"), ("reserved", "u1", (10,))])
+FIN_RESULT_DTYPE = np.dtype([("events", "<u4"), ("state", "<u4"), ("seq", "<u4"), ("interval", "<u4")])
+TCP_ESTABLISHED, TCP_FIN_WAIT_1, TCP_FIN_WAIT_2, TCP_CLOSED = 3, 4, 5, 6
+TCP_CLOSE_WAIT, TCP_CLOSING, TCP_LAST_ACK, TCP_TIME_WAIT = 7, 8, 9, 10
+FIN_CLOSE_REQ, FIN_MAX_MS, FIN_2MSL_MS = 1, 60000, 60000
+FIN_EV_PEER_FIN, FIN_EV_ACK_OWED, FIN_EV_SENT, FIN_EV_RESENT = 0x01, 0x02, 0x04, 0x08
+FIN_EV_ACKED, FIN_EV_TW_DONE, FIN_EV_LATE_WRITE = 0x10, 0x20, 0x40
+assert FIN_FLOW_DTYPE.itemsize == 32 and FIN_RESULT_DTYPE.itemsize == 16
+
+
+def fin_flows(flows: np.ndarray) -> np.ndarray:
+    """Fresh lvlip_fin_flow states for the planned flows: ESTABLISHED, base =
+    rcv_nxt."""
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    x = np.zeros(flows.size, dtype=FIN_FLOW_DTYPE)
+    x["base"], x["state"] = flows["rcv_nxt"], TCP_ESTABLISHED
+    return x
+
+
+def fin_check(fin: np.ndarray, flows: np.ndarray) -> None:
+    """lvlip_fin_check: ValueError for a state the calls refuse."""
+    _planned(fin, FIN_FLOW_DTYPE, "fin: a contiguous FIN_FLOW_DTYPE array", writeable=False)
+    flows = np.ascontiguousarray(flows, dtype=LRO_FLOW_DTYPE)
+    if fin.size != flows.size:
+        raise ValueError("one close state per flow")
+    if _lib.lvlip_fin_check(_aptr(fin), _aptr(flows), flows.size) != OK:
+        raise ValueError("refused close state (state, reserved, interval, base, too many)")
+
+
+def fin_cpu(flows: np.ndarray, gin: np.ndarray, rec, snd: np.ndarray, push: np.ndarray, rto: np.ndarray,
+            fin: np.ndarray, close, now: int, out: Optional[np.ndarray] = None):
+    """lvlip_fin_cpu: one round of the connections' close, IN PLACE in flows
+    (rcv_nxt), snd (snd_nxt) and fin.  gin (LRO_RESULT_DTYPE) is what ack_*
+    would have been given, rec (LRO_REC_DTYPE, or None) the round's records,
+    close one uint8 per flow or None.  Returns (out, fd_out, gate, res): the
+    FINs' buffer (PERSIST_SLOT bytes per flow; the caller's `out`, or a new
+    zeroed one), FRAME_DESC_DTYPE, LRO_RESULT_DTYPE for ack_* and
+    FIN_RESULT_DTYPE per flow."""
+    _planned(flows, LRO_FLOW_DTYPE, "flows: a writeable contiguous LRO_FLOW_DTYPE array")
+    _planned(snd, SND_FLOW_DTYPE, "snd: a writeable contiguous SND_FLOW_DTYPE array")
+    _planned(fin, FIN_FLOW_DTYPE, "fin: a writeable contiguous FIN_FLOW_DTYPE array")
+    gin = np.ascontiguousarray(gin, dtype=LRO_RESULT_DTYPE)
+    push = np.ascontiguousarray(push, dtype=PUSH_FLOW_DTYPE)
+    rto = np.ascontiguousarray(rto, dtype=RTO_FLOW_DTYPE)
+    rec = None if rec is None else np.ascontiguousarray(rec, dtype=LRO_REC_DTYPE)
+    close = None if close is None else np.ascontiguousarray(close, dtype=np.uint8)
+    n = flows.size
+    if any(a.size != n for a in (gin, snd, push, rto, fin)) or (close is not None and close.size != n):
+        raise ValueError("one result, send side, write side, timer state, close state and close byte per flow")
+    out = _out_u8(out, PERSIST_SLOT * n)
+    if not out.flags.writeable:
+        raise ValueError("out: writeable")
+    fd_out = np.zeros(n, dtype=FRAME_DESC_DTYPE)
+    gate = np.zeros(n, dtype=LRO_RESULT_DTYPE)
+    res = np.zeros(n, dtype=FIN_RESULT_DTYPE)
+    _check(_lib.lvlip_fin_cpu(_aptr(flows), _aptr(gin), _aptr(rec), 0 if rec is None else rec.size, _aptr(snd),
+                              _aptr(push), _aptr(rto), _aptr(fin), n, _aptr(close), now & 0xFFFFFFFF, _aptr(out),
+                              _aptr(fd_out), _aptr(gate), _aptr(res)), "lvlip_fin_cpu")
+    return out, fd_out, gate, res
+
+
+def fin_workspace_bytes(nflows: int) -> int:
+    """lvlip_fin_workspace_bytes: the device workspace fin_dev needs."""
+    return int(_lib.lvlip_fin_workspace_bytes(nflows))
+
+
+def fin_dev(flows_t, gin_t, rec_t, snd_t, push_t, rto_t, fin_t, close_t, now: int, out_t, gate_t, ws_t,
+            fd_out_t=None, res_t=None, stream=None):
+    """lvlip_fin_dev on CUDA uint8 tensors: flows_t 48, gin_t 48, snd_t 32,
+    push_t 112, rto_t 32 and fin_t 32 bytes per flow (flows_t's rcv_nxt, snd_t's
+    snd_nxt and fin_t updated in place); rec_t 16 bytes per record or None;
+    close_t one byte per flow or None; out_t PERSIST_SLOT bytes per flow at any
+    alignment; gate_t 48 bytes per flow, written; ws_t fin_workspace_bytes.
+    Returns (fd_out_t, res_t): 16 bytes per flow each (new tensors unless
+    given).  A memset and two launches on `stream` (default: current),
+    asynchronous."""
+    nflows = _nbytes(flows_t) // LRO_FLOW_DTYPE.itemsize
+    n = _records(rec_t, LRO_REC_DTYPE.itemsize)
+    _need(gin_t, "gin_t", LRO_RESULT_DTYPE.itemsize, nflows, "flow")
+    _need(snd_t, "snd_t", SND_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(push_t, "push_t", PUSH_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(rto_t, "rto_t", RTO_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(fin_t, "fin_t", FIN_FLOW_DTYPE.itemsize, nflows, "flow")
+    _need(close_t, "close_t", 1, nflows, "flow", optional=True)
+    _need(out_t, "out_t", PERSIST_SLOT, nflows, "flow")
+    _need(gate_t, "gate_t", LRO_RESULT_DTYPE.itemsize, nflows, "flow")
+    if _nbytes(ws_t) < fin_workspace_bytes(nflows):
+        raise ValueError("ws_t: fin_workspace_bytes(nflows) bytes")
+    fd_out_t = _result(fd_out_t, "fd_out_t", 16, nflows, "flow", flows_t.device)
+    res_t = _result(res_t, "res_t", FIN_RESULT_DTYPE.itemsize, nflows, "flow", flows_t.device)
+    s = _stream(stream, flows_t.device)
+    _check(_lib.lvlip_fin_dev(flows_t.data_ptr(), gin_t.data_ptr(), _tptr(rec_t, n), n, snd_t.data_ptr(),
+                              push_t.data_ptr(), rto_t.data_ptr(), fin_t.data_ptr(), nflows, _tptr(close_t),
+                              now & 0xFFFFFFFF, out_t.data_ptr(), fd_out_t.data_ptr(), gate_t.data_ptr(),
+                              res_t.data_ptr(), ws_t.data_ptr(), s.cuda_stream), "lvlip_fin_dev")
+    return fd_out_t[:16 * nflows], res_t[:FIN_RESULT_DTYPE.itemsize * nflows]
 
 
 # ----------------------------------------------------- Group 4: several GPUs --
